@@ -8,7 +8,10 @@ bf16 activation storage (fp32 accumulate, fp32 master weights), on N MI355X of o
 One "step" = one full train iteration of the hot path over one synthetic batch that is already resident
 in HBM: forward (train-mode BatchNorm) -> fused losses l1 + 0.1*add_loss + 0.2*cross_entropy and their
 gradients -> hand-derived backward -> (N > 1: bucketed RCCL all-reduce overlapped with the backward) ->
-AdamW update.  Prints ONE JSON line (rank 0).  Also reported on the same line:
+AdamW update.  Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, the W
+warm-up steps, the K timed steps (with --dump-outputs DIR, then what the last of them computed as DIR/<name>.npy).
+With --full, also measured and reported on the same line:
+  host_issue_ms_per_step (config) the host time to enqueue one step, from two extra untimed steps ahead of the timed ones
   roofline      the depthwise kernels (the ones the north-star names), each family -- forward / backward x
                 stride 1 / 2, by its rocprof kernel name -- timed with HIP events on the launch stream inside
                 the timed steps: algorithmic HBM bytes / measured time vs 8 TB/s; the headline entry is the
@@ -142,10 +145,16 @@ def parse():
     ap.add_argument('--engine', action='store_true', help='drive models.engine.Net + the loss / optimizer kernels directly '
                     'instead of going through the reference-shaped API (build_model / build_optimizer / LossManager / '
                     'Trainer.train_step), which is what the headline number is measured through')
-    ap.add_argument('--roofline-every', type=int, default=4, help='the depthwise launches of every n-th timed step carry '
+    ap.add_argument('--roofline-every', type=int, default=4, help='--full: the depthwise launches of every n-th timed step carry '
                     'HIP-event pairs (an event pair per launch on all steps costs ~0.25 ms per step)')
     ap.add_argument('--per-launch', action='store_true', help='print every conv launch of one step (stderr)')
     ap.add_argument('--profile-all', action='store_true', help='time every kernel family, print a table to stderr')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: the host issue '
+                    'time of a step (two extra untimed steps), the roofline block (HIP-event pairs on the convolution launches '
+                    'of sampled timed steps) and the CPU baseline (a child process of up to 150 s; --no-cpu-baseline drops it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='', help='after the timed steps, write what the last of them '
+                    'computed as DIR/<name>.npy (float32 / float64; an array of more than %d elements as a fixed, seeded '
+                    'sample of them)' % DUMP_MAX_ELEMS)
     return ap.parse_args()
 
 
@@ -207,6 +216,25 @@ def cpu_baseline_guarded(args):
     except Exception as e:  # noqa: BLE001  (timeout, crash, unparsable output)
         return dict(value=None, unit='crops/s', cores=min(os.cpu_count() or 1, args.cpu_threads or CPU_THREADS_BEST), kind='port',
                     sample=f'CPU leg did not finish within its 150 s limit ({type(e).__name__})')
+
+
+DUMP_MAX_ELEMS = 1 << 22    # per array (16 MB in float32): the largest model's weights and gradient stay under 64 MB in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy, float64 where the value is (host floats, integer counters), float32 otherwise.
+    An array of more than DUMP_MAX_ELEMS elements is written as the same seeded sample of its flattened elements on every run."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu()
+            a = (a.float() if a.is_floating_point() and a.dtype != torch.float64 else a.double()).numpy()
+        else:
+            a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(d, name + '.npy'), a)
 
 
 def conv_source_hash():
@@ -355,6 +383,7 @@ def main():
         kp, lg = net.forward(imgs[j], cats[j], train=False)
         N.call('t3d_loss_fwd_bwd', cfg, N.ptr(kp), N.ptr(gts[j]), N.ptr(lg), N.ptr(cats[j]), N.ptr(out), None, None, B, 9,
                N.stream())
+        last[0] = (kp, lg)
 
     def step(i):
         if args.eval:
@@ -370,6 +399,7 @@ def main():
         net.backward(dkp, dlg)
         sync.finish(scale=False)
         opt.step()
+        last[0] = (kp, lg)
 
     def barrier():
         torch.cuda.synchronize()
@@ -398,11 +428,13 @@ def main():
     net._side = side
     # host cost of a step: time to ENQUEUE two steps into an empty queue (inside the timed region the host runs ahead
     # until HIP's queue back-pressure stalls it, which would be measured instead)
-    barrier()
-    t0 = time.perf_counter()
-    step(0)
-    step(1)
-    t_issue = (time.perf_counter() - t0) / 2
+    t_issue = None
+    if args.full:
+        barrier()
+        t0 = time.perf_counter()
+        step(0)
+        step(1)
+        t_issue = (time.perf_counter() - t0) / 2
     if args.profile_all and rank == 0:
         tot = sum(v['ms'] for v in fam.values())
         for k, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms']):
@@ -418,20 +450,22 @@ def main():
                   file=sys.stderr)
         N.timer = None
 
-    # ---- timed region: exactly K steps; the depthwise launches (main stream) carry HIP-event pairs
+    # ---- timed region: exactly K steps; with --full the depthwise launches (main stream) carry HIP-event pairs
     every = max(1, args.roofline_every)
     # ... and on three steps spread over the region EVERY convolution launch does (roofline.families): ~200 pairs per step cost
     # ~1 ms on that step, so it is three steps and not every 4th
     full_steps = sorted({args.steps // 4, args.steps // 2, (3 * args.steps) // 4}) if args.steps >= 8 else [0]
     # kernel_exact: the event pair is attached to the depthwise kernel's own dispatch (begin-to-end of the kernel, as rocprofv3
     # reports it), not recorded around the launch call (which adds 5-9 us of event packets and dispatch latency)
-    rtimer = N.KernelTimer(set(DW_ENTRIES), prealloc=2 * 40 * ((args.steps + every - 1) // every), kernel_exact=not os.environ.get('T3D_EVENTS_AROUND'))
+    rtimer = (N.KernelTimer(set(DW_ENTRIES), prealloc=2 * 40 * ((args.steps + every - 1) // every), kernel_exact=not os.environ.get('T3D_EVENTS_AROUND'))
+              if args.full else None)
     N.timer = None
     # the API path replays a recorded step plan (trainer/step_plan.py: one t3d_plan_run per step): the event pairs are then
     # attached by the replay itself, to the same launches through the same t3d_set_launch_events
     sp = trainer._step_plan() if (use_api and not args.eval) else None
+    replayed = sp is not None and sp.rec is not None
     ptimer = None
-    if sp is not None and sp.rec is not None:
+    if args.full and replayed:
         from torchdet3d.trainer.step_plan import PlanTiming
         ncalls = lambda names: sum(1 for c in sp.rec.calls if c[0] in names)
         ptimer = sp.timing = PlanTiming(sp, {'dw': DW_ENTRIES, 'all': FAMILY_ENTRIES},
@@ -458,14 +492,15 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
-    fam_launches, fam_steps = [], 0
+    fam_launches, fam_steps, launches, nsampled = [], 0, [], 0
     if ptimer is not None:
         ptimer.close()
         sp.timing = None
         fam_launches, fam_steps = ptimer.per_launch('all'), ptimer.steps('all')
+        launches, nsampled = ptimer.per_launch('dw'), ptimer.steps('dw')
+    elif rtimer is not None:
+        launches, nsampled = rtimer.per_launch(), (args.steps + every - 1) // every
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    launches = ptimer.per_launch('dw') if ptimer is not None else rtimer.per_launch()
-    nsampled = ptimer.steps('dw') if ptimer is not None else (args.steps + every - 1) // every
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -474,6 +509,19 @@ def main():
     assert loss == loss or os.environ.get('T3D_ABLATE'), 'loss is NaN'
     # (the clamp-form ReLU6 of the 16-bit kernels maps a NaN pre-activation to 0: a diverged step is seen in the BatchNorm sums)
     assert args.eval or not net.nonfinite() or os.environ.get('T3D_ABLATE'), 'a BatchNorm saw non-finite batch sums'
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the returned metrics (the API path) or the engine's
+        # outputs, and after a train step the updated master weights, their gradient and the BatchNorm running statistics
+        if args.eval and use_api:
+            arrays = {'per_class_metrics': [list(r) for r in last[0][0]], 'metrics': last[0][1:]}
+        elif use_api:
+            arrays = {'metrics': [last[0][k] for k in ('loss', 'ADD', 'SADD', 'acc')]}
+        else:
+            arrays = {'keypoints': last[0][0], 'logits': last[0][1], 'loss_terms': out}
+        if not args.eval:
+            arrays.update(weights=net.flat, grads=net.gflat,
+                          bn_buffers=torch.cat([b.double().reshape(-1) for b in net.buffers.values()]))
+        dump_outputs(args.dump_outputs, arrays)
 
     eval_dt = None
     if args.eval:
@@ -492,13 +540,13 @@ def main():
                                       if args.eval else
                                       f'train step (fwd + l1/add/CE losses + bwd + AdamW{" + RCCL grad all-reduce" if world > 1 else ""})')
                                    + f', {S}x{S} crops, per-GPU batch {B}', 'global_batch': B * world, 'parallelism': f'dp{world}',
-                       'final_loss': round(loss, 5), 'host_issue_ms_per_step': round(t_issue * 1e3, 3),
+                       'final_loss': round(loss, 5), 'host_issue_ms_per_step': round(t_issue * 1e3, 3) if t_issue is not None else None,
                        'driven_through': ((('torchdet3d.builders.build_model / Evaluator.val_step' if args.eval_sync else 'torchdet3d.builders.build_model / Evaluator.val_enqueue + PendingMetrics.result (= Evaluator.val)') if args.eval else
                                            'torchdet3d.builders.build_model / build_optimizer / LossManager / Trainer.train_step')
                                           if use_api else 'models.engine.Net + loss / optimizer entry points'),
                        'step_form': (('one t3d_plan_run call per step (recorded step plan: %d launches, %d stream forks)'
                                       % (N.lib().t3d_plan_num_ops(sp.rec.plan, 0), N.lib().t3d_plan_num_ops(sp.rec.plan, 1)))
-                                     if ptimer is not None else
+                                     if replayed else
                                      ('eval-mode forward replayed from a recorded plan (one t3d_plan_run, %d launches) + the metric launches'
                                       % N.lib().t3d_plan_num_ops(model._forward_plan().rec.plan, 0))
                                      if (args.eval and use_api and getattr(model._forward_plan(), 'rec', None) is not None) else
@@ -582,7 +630,7 @@ def main():
             res['config']['parity_note'] = ('bf16 inference is NOT parity-gated: 3-D IoU deviates by 2e-3 (sigma 0.024) .. 4e-3 from the fp32 '
                                             'oracle (bound 1e-3; tests/test_gpu_bf16_gate.py); the default eval engine (fp32 storage) '
                                             'meets it')
-        if world == 1 and not args.no_cpu_baseline and not args.eval:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.eval:
             res['cpu_baseline'] = cpu_baseline_guarded(args)
         print(json.dumps(res), flush=True)
     if dist.is_initialized():

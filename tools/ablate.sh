@@ -3,7 +3,7 @@
 # numerics, valid step time).  Output: gpurun_out/ablate.txt
 cd "$(dirname "$0")/.." && mkdir -p gpurun_out
 out=gpurun_out/ablate.txt; : > $out
-run() { echo "== $1" >> $out; env $2 python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+run() { echo "== $1" >> $out; env $2 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1]); r = d.get('roofline', {})
 print(d['ms_per_step'], d['config']['step_ms_min_med_max'], r.get('frac'), [(x['kernel'], x['avg_launch_us']) for x in r.get('depthwise', [])])" >> $out 2>&1; }

@@ -2,23 +2,23 @@
 # everything the round's profiles/ are made of, in one GPU call.  usage: tools/profile_round.sh <tag> <commit>
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 tag=${1:-r6_g}; commit=${2:-?}; o=gpurun_out/$tag; mkdir -p $o
-python3 bench.py --steps 30 --warmup 8 > $o/bench_bf16.json 2> $o/bench_bf16.err
+python3 bench.py --full --steps 30 --warmup 8 > $o/bench_bf16.json 2> $o/bench_bf16.err
 python3 bench.py --steps 30 --warmup 8 --no-cpu-baseline --profile-all > /dev/null 2> $o/bench_bf16_families.txt
 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --per-launch > /dev/null 2> $o/bench_bf16_per_launch.txt
-python3 bench.py --steps 10 --warmup 3 --dtype f32 --no-cpu-baseline > $o/bench_f32.json 2> /dev/null
-python3 bench.py --steps 30 --warmup 8 --eval --no-cpu-baseline > $o/bench_eval.json 2> /dev/null
-python3 bench.py --steps 30 --warmup 8 --eval --eval-dtype bf16 --no-cpu-baseline > $o/bench_eval_bf16_optin.json 2> /dev/null
-python3 bench.py --steps 30 --warmup 8 --eval --eval-sync --no-cpu-baseline > $o/bench_eval_val_step.json 2> /dev/null
-python3 bench.py --steps 30 --warmup 8 --eval --eval-sync --eval-dtype bf16 --no-cpu-baseline > $o/bench_eval_bf16_optin_val_step.json 2> /dev/null
-T3D_F32_TILED=1 python3 bench.py --steps 30 --warmup 8 --eval --no-cpu-baseline > $o/bench_eval_f32_tiled_kernel.json 2> /dev/null
-python3 bench.py --steps 20 --warmup 5 --model mobilenetv3_large --no-cpu-baseline > $o/bench_mnv3_large.json 2> /dev/null
-python3 bench.py --steps 20 --warmup 5 --model mobilenetv3_small --no-cpu-baseline > $o/bench_mnv3_small.json 2> /dev/null
-python3 bench.py --steps 30 --warmup 8 --eval --eval-dtype f16 --no-cpu-baseline > $o/bench_eval_f16.json 2> /dev/null
-python3 bench.py --steps 20 --warmup 5 --model resnet50 --batch 64 --no-cpu-baseline > $o/bench_resnet50.json 2> /dev/null
-python3 bench.py --steps 30 --warmup 8 --engine --no-cpu-baseline > $o/bench_bf16_engine_loop.json 2> /dev/null
-T3D_STEP_PLAN=0 python3 bench.py --steps 30 --warmup 8 --no-cpu-baseline > $o/bench_bf16_direct_step.json 2> /dev/null
-T3D_PLAN_HANDOFF=0 python3 bench.py --steps 30 --warmup 8 --no-cpu-baseline > $o/bench_bf16_event_forks.json 2> /dev/null
-T3D_IMPLICIT3=1 python3 bench.py --steps 20 --warmup 5 --model resnet50 --batch 64 --no-cpu-baseline > $o/bench_resnet50_implicit3x3.json 2> /dev/null
+python3 bench.py --full --steps 10 --warmup 3 --dtype f32 --no-cpu-baseline > $o/bench_f32.json 2> /dev/null
+python3 bench.py --full --steps 30 --warmup 8 --eval --no-cpu-baseline > $o/bench_eval.json 2> /dev/null
+python3 bench.py --full --steps 30 --warmup 8 --eval --eval-dtype bf16 --no-cpu-baseline > $o/bench_eval_bf16_optin.json 2> /dev/null
+python3 bench.py --full --steps 30 --warmup 8 --eval --eval-sync --no-cpu-baseline > $o/bench_eval_val_step.json 2> /dev/null
+python3 bench.py --full --steps 30 --warmup 8 --eval --eval-sync --eval-dtype bf16 --no-cpu-baseline > $o/bench_eval_bf16_optin_val_step.json 2> /dev/null
+T3D_F32_TILED=1 python3 bench.py --full --steps 30 --warmup 8 --eval --no-cpu-baseline > $o/bench_eval_f32_tiled_kernel.json 2> /dev/null
+python3 bench.py --full --steps 20 --warmup 5 --model mobilenetv3_large --no-cpu-baseline > $o/bench_mnv3_large.json 2> /dev/null
+python3 bench.py --full --steps 20 --warmup 5 --model mobilenetv3_small --no-cpu-baseline > $o/bench_mnv3_small.json 2> /dev/null
+python3 bench.py --full --steps 30 --warmup 8 --eval --eval-dtype f16 --no-cpu-baseline > $o/bench_eval_f16.json 2> /dev/null
+python3 bench.py --full --steps 20 --warmup 5 --model resnet50 --batch 64 --no-cpu-baseline > $o/bench_resnet50.json 2> /dev/null
+python3 bench.py --full --steps 30 --warmup 8 --engine --no-cpu-baseline > $o/bench_bf16_engine_loop.json 2> /dev/null
+T3D_STEP_PLAN=0 python3 bench.py --full --steps 30 --warmup 8 --no-cpu-baseline > $o/bench_bf16_direct_step.json 2> /dev/null
+T3D_PLAN_HANDOFF=0 python3 bench.py --full --steps 30 --warmup 8 --no-cpu-baseline > $o/bench_bf16_event_forks.json 2> /dev/null
+T3D_IMPLICIT3=1 python3 bench.py --full --steps 20 --warmup 5 --model resnet50 --batch 64 --no-cpu-baseline > $o/bench_resnet50_implicit3x3.json 2> /dev/null
 python3 tools/time_expdw.py > $o/expdw_fused_forward_timings.txt 2>&1
 python3 tools/time_pw_f32.py > $o/pw_f32_reg_vs_tiled.txt 2>&1
 bash tools/time_kernels.sh > $o/isolated_kernel_timings.txt 2>&1
@@ -26,7 +26,7 @@ python3 tools/bench_two_stage.py --detector 2> /dev/null | tail -1 > $o/two_stag
 python3 tools/bench_two_stage.py --dets 64 2> /dev/null | tail -1 >> $o/two_stage_pipeline_bench.jsonl
 # rocprofv3 kernel trace + stats of the default bench (the program itself after `--`)
 d=gpurun_out/trace_$tag; rm -rf $d
-rocprofv3 --kernel-trace --stats --output-format csv -d $d -o t -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_bf16_under_rocprof.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $d -o t -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_bf16_under_rocprof.json 2> /dev/null
 find $d -name "*kernel_stats.csv" -exec cp {} $o/kernel_stats.csv \;
 python3 tools/trace_streams.py $(find $d -name "*kernel_trace.csv") > $o/stream_timeline.txt 2>&1
 python3 tools/trace_summary.py $(find $d -name "*kernel_trace.csv") > $o/step_kernel_table.txt 2>&1
