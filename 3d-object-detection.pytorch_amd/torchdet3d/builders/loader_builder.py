@@ -1,9 +1,10 @@
-"""Loader boundary.  The reference's Objectron dataset + albumentations pipeline
-(torchdet3d/builders/loader_builder.py:14-36, dataloaders/objectron_main.py) is CPU data preparation and out of
-scope for this build; what the hot path needs is its OUTPUT CONTRACT
-(objectron_main.py:51-96 + utils/transforms.py:103-114): batches `(imgs f32 [B,3,H,W] normalised, gt_kp f32
-[B,9,2] in [0,1], gt_cats int64 [B])`.  `SyntheticCrops` produces exactly that; `build_loader` serves it when
-`cfg.data.root == 'synthetic'`.
+"""Loader boundary (torchdet3d/builders/loader_builder.py:14-68 of the reference).
+
+`cfg.data.root == 'synthetic'`: `SyntheticCrops`, batches `(imgs f32 [B,3,H,W] normalised, gt_kp f32 [B,9,2] in [0,1], gt_cats
+int64 [B])` -- the reference's output contract (objectron_main.py:51-96 + utils/transforms.py:103-114) without a dataset.
+Any other root: the Objectron dataset (dataloaders/objectron.py) with the config's pipelines compiled by
+`build_augmentations` and applied on the GPU (`GpuAugmentLoader`, one `t3d_augment_crops_u8` launch per batch): batches
+`(imgs uint8 [B,oh,ow,3] NHWC on the device, gt_kp f32 [B,9,2], gt_cats int64 [B])`, normalised inside the stem.
 
 One process per GPU (an unchanged scripts/main.py under `python -m torch.distributed.run`; `build_model`, called first by
 main.py:46, has joined the process group by the time main.py:63 builds the loaders): the reference's `nn.DataParallel`
@@ -32,8 +33,7 @@ class SyntheticCrops(torch.utils.data.Dataset):
 
 def build_loader(config, mode='train'):
     if config.data.root != 'synthetic':
-        raise NotImplementedError('only the synthetic crop source is built (cfg.data.root = "synthetic"); the '
-                                  'Objectron JSON/albumentations loader is out of scope')
+        return _build_objectron_loaders(config)
     n = config.data.synthetic_len or 64
     size = tuple(config.data.resize) if config.data.resize else (224, 224)
     mk = lambda seed: SyntheticCrops(n, size, config.model.num_classes or 9, seed)
@@ -55,4 +55,29 @@ def build_loader(config, mode='train'):
         val = torch.utils.data.DataLoader(torch.utils.data.Subset(dv, range(rk, len(dv), world)),
                                           batch_size=max(vb // world, 1), shuffle=False)
     test = torch.utils.data.DataLoader(mk(3), batch_size=1, shuffle=False)
+    return train, val, test
+
+
+def _build_objectron_loaders(config):
+    from ..dataloaders import GpuAugmentLoader, Objectron, build_augmentations
+    train_tf, test_tf = build_augmentations(config)
+    root, cats = config.data.root, config.data.category_list or 'all'
+    tb, vb = config.data.train_batch_size or 8, config.data.val_batch_size or 8
+    nw = config.data.num_workers or 0
+    seed = int(getattr(getattr(config, 'utils', None), 'random_seeds', 0) or 0)
+    world, rk = world_size(), rank()
+    if tb % world:
+        raise ValueError(f'data.train_batch_size = {tb} is the GLOBAL batch (scripts/main.py:60-61 scatters it over the '
+                         f'replicas): it must be divisible by the {world} ranks of this launch')
+    ds = Objectron(root, mode='train', transform=train_tf, category_list=cats)
+    # a shuffle that depends on (seed, epoch) only -- one rank is a DistributedSampler of one replica
+    sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rk, shuffle=True, seed=seed,
+                                                              drop_last=True)
+    train = GpuAugmentLoader(ds, train_tf, tb // world, sampler=sampler, num_workers=nw, drop_last=True, seed=seed, rank=rk)
+    dv = Objectron(root, mode='val', transform=test_tf, category_list=cats)
+    if world > 1:
+        dv = torch.utils.data.Subset(dv, range(rk, len(dv), world))
+    val = GpuAugmentLoader(dv, test_tf, max(vb // world, 1), num_workers=nw, seed=seed, rank=rk)
+    dt = Objectron(root, mode='test', transform=test_tf, category_list=cats)
+    test = GpuAugmentLoader(dt, test_tf, 1, num_workers=nw, seed=seed, rank=rk)
     return train, val, test

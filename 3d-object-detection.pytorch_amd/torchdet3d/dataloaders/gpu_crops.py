@@ -5,8 +5,8 @@ its nine annotated keypoints (`crop`, :98-126: keypoints clipped 3 px inside the
 to the frame), resizes the crop (albumentations `Resize` -> cv.resize) and normalises the keypoints by the final image size
 (`utils/transforms.py:112-114`, `utils/utils.py:231-240`).  Here the box arithmetic stays on the host (nine points per
 object) and crop + resize run as one launch per frame (`t3d_crop_resize_u8`); the crops stay uint8 NHWC and go straight into
-`model(x, cats)` (normalised inside the stem).  Augmentations (flip / colour / blur, `builders/loader_builder.py`) are CPU
-data preparation and not rebuilt.
+`model(x, cats)` (normalised inside the stem).  The dataset itself, with the config's augmentations on the GPU, is
+`dataloaders/objectron.py` + `dataloaders/gpu_loader.py`.
 """
 import numpy as np
 import torch

@@ -230,6 +230,30 @@ int t3d_ir_block_eval(const void* x, const void* w1, const float* scale1, const 
 int t3d_crop_resize_u8(const unsigned char* frame, const int* rects, unsigned char* out, int n, int H, int W, int oh, int ow,
                        void* stream);
 
+/* The reference's training augmentations of a batch of crops, one launch (csrc/augment.hip; replaces the albumentations
+ * pipeline of dataloaders/objectron_main.py:71-80 as builders/loader_builder.py:38-68 compiles configs/default_config.py:31-37):
+ * per sample, in this order and with uint8 rounding after each step that yields an image,
+ *   resize to (oh, ow)  cv::resize INTER_LINEAR on 8-bit data (t3d_crop_resize_u8's arithmetic),
+ *   T3D_AUG_FLIP        mirror the columns (A.HorizontalFlip),
+ *   T3D_AUG_LUT         lut[i] = (uint8) clip(float32(i) * alpha + beta255, 0, 255) (A.RandomBrightnessContrast, uint8),
+ *   T3D_AUG_ROTATE      cv::warpAffine INTER_LINEAR, border 0, through the INVERSE map m (utils/transforms.py:50-89),
+ *   T3D_AUG_SWAP_RB     RGB -> BGR (a pipeline without convert_color hands the model cv.imread's order).
+ * src: the crops, each h rows of w*3 bytes, packed at `offset`; src_bytes bounds them (a record outside it, or with h or w
+ * < 1, gives a zero image).  samples: [B] t3d_aug_sample in DEVICE memory.  out [B, oh, ow, 3] uint8, 4-byte aligned.
+ * With no flag set the output equals t3d_crop_resize_u8 of the same crop, bit for bit. */
+enum { T3D_AUG_FLIP = 1, T3D_AUG_LUT = 2, T3D_AUG_ROTATE = 4, T3D_AUG_SWAP_RB = 8 };
+typedef struct {
+  long long offset;      /* byte offset of the crop in src */
+  int h, w;              /* crop size */
+  int flags;             /* T3D_AUG_* */
+  float alpha;           /* contrast (T3D_AUG_LUT) */
+  float beta255;         /* brightness * 255, rounded to float32 once (T3D_AUG_LUT) */
+  int reserved;
+  double m[6];           /* T3D_AUG_ROTATE: output pixel -> resized-image coordinate, row-major 2x3 (fp64) */
+} t3d_aug_sample;        /* 80 bytes */
+int t3d_augment_crops_u8(const unsigned char* src, long long src_bytes, const void* samples, unsigned char* out, int B, int oh,
+                         int ow, void* stream);
+
 /* Materialise a block output:  z = act(scale*y + shift) + residual   (residual may be NULL; scale NULL = identity).
  * Replaces the BatchNorm normalise pass + `x + self.conv(x)` (mobilenetv3.py:159,162-164). y,z,residual [M,C]. */
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
