@@ -325,6 +325,10 @@ class Net:
             rows = [list(r) for r in extra_rows] + [[p, nb] for (p, nb) in sorted(keys)]
             desc[dk] = torch.tensor(rows, dtype=torch.int64, device=self.device) if rows else None
         if desc[dk] is not None:
+            if N.recorder is not None:
+                # a plan holds the descriptor's address as a plain word: it must outlive this dict's entry, which the
+                # next pass at another batch size replaces (the old rows still list exactly what the recorded step clears)
+                N.recorder.keep.append(desc[dk])
             N.call('t3d_zero_batched', N.ptr(desc[dk]), desc[dk].shape[0], N.stream())
 
     def _zero(self, t):
@@ -336,6 +340,8 @@ class Net:
             d = zd.get((t.data_ptr(), nb))
             if d is None:
                 d = zd[(t.data_ptr(), nb)] = torch.tensor([[t.data_ptr(), nb]], dtype=torch.int64, device=self.device)
+            if N.recorder is not None:
+                N.recorder.keep.append(d)
             N.call('t3d_zero_batched', N.ptr(d), 1, N.stream())
         else:
             if N.recorder is not None:

@@ -8,11 +8,15 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize('name,B,HW', [('mobilenetv2', 128, 224), ('mobilenetv2', 100, 112), ('mobilenetv3_large', 96, 224)])
+@pytest.mark.parametrize('name,B,HW', [('mobilenetv2', 128, 224), ('mobilenetv2', 100, 112), ('mobilenetv3_large', 96, 224),
+                                       # off the square grid (HW = (H, W)): 10 x 8 / 5 x 4 planes; 7 x 7 / 4 x 4 at B = 82
+                                       pytest.param('mobilenetv2', 100, (160, 128), id='mobilenetv2-100-160x128'),
+                                       pytest.param('mobilenetv3_large', 82, (100, 100), id='mobilenetv3_large-82-100x100')])
 def test_fused_eval_blocks_match_the_layer_by_layer_path(name, B, HW):
     from oracle.weights import make_inputs, make_state_dict
     from torchdet3d.models.engine import Net
-    imgs, _, cats = make_inputs(B, HW, HW, 9)
+    H, W = HW if isinstance(HW, tuple) else (HW, HW)
+    imgs, _, cats = make_inputs(B, H, W, 9)
     sd = make_state_dict(name, 9)
     outs, launches = {}, {}
     for fused in (True, False):

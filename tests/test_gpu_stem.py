@@ -47,6 +47,11 @@ def test_uint8_crops_through_the_model_match_the_normalised_fp32_path():
     """build_model: model(uint8 NHWC crops) == model((u/255 - mean)/std as fp32 NCHW) up to the last bit of the
     normalisation arithmetic, in eval and through one train step (fp32 storage, where a last-bit input difference stays a
     last-bit difference; under bf16 storage train-mode BatchNorm amplifies it chaotically, test_gpu_bf16_gate.py)."""
+    uint8_crops_match_the_fp32_path(128, 128)
+
+
+def uint8_crops_match_the_fp32_path(H, W):
+    """The check above on 16 crops of H x W (tests/test_gpu_model_shapes.py runs it off the square grid)."""
     from oracle.weights import make_state_dict
     from test_host_logic import _cfg
     from torchdet3d.builders import build_loss, build_model, build_optimizer
@@ -54,7 +59,7 @@ def test_uint8_crops_through_the_model_match_the_normalised_fp32_path():
     cfg = _cfg('mobilenetv2')
     cfg.model.storage_dtype = 'f32'
     g = torch.Generator().manual_seed(4)
-    u = torch.randint(0, 256, (16, 128, 128, 3), generator=g, dtype=torch.uint8)
+    u = torch.randint(0, 256, (16, H, W, 3), generator=g, dtype=torch.uint8)
     xn = ((u.float() * (1.0 / 255.0) - torch.tensor(MEAN)) / torch.tensor(STD)).permute(0, 3, 1, 2).contiguous()
     cats = torch.randint(0, 9, (16,), generator=g).cuda()
     gt = torch.rand(16, 9, 2, generator=g).cuda()
