@@ -39,7 +39,7 @@ struct Dw3BArgs {
   long long rstride;
   int dw_slots;  // > 0: the weight gradient goes to one slot per workgroup (t3d_set_dw_slots; common.h: t3d_dw_flush)
   int* dw_used;
-  int noflush;   // profiling ablation only (T3D_DEBUG_NOFLUSH): skip the end-of-block reduction
+  int noflush;   // always 0 (was a profiling ablation); the test on it stays so the kernels' code stays as measured
   const T3dFold* fold;  // requested BatchNorm-backward finalize of (alpha, beta, gamma), derived in the prologue (common.h)
 };
 
@@ -756,8 +756,7 @@ int launch_s1c(Dw3BArgs& a, hipStream_t st) {
   dim3 grid;
   // tools/sweep_dwb.sh: the 4-channel variant needs AGPR spill space (1 wave/SIMD) and is best with one block per CU;
   // the 2-channel variant fits 2 waves/SIMD and is best with two (every extra block is one more flush)
-  static const int tb_env = getenv("T3D_DW_TB") ? atoi(getenv("T3D_DW_TB")) : 0;      // (sweep knob, tools/scratch/sweep_tb.sh)
-  const int target_blocks = tb_env ? tb_env : (CH == 2 && two_col ? 512 : 256);
+  const int target_blocks = CH == 2 && two_col ? 512 : 256;
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   const int nth = 256;   // 512-thread blocks measured 4-5x slower (register budget)
@@ -792,7 +791,6 @@ int launch_s1c(Dw3BArgs& a, hipStream_t st) {
     a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
   }
   const size_t lds = (size_t)22 * ((two_col && a.slab) ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64 reduction scratch (before it: [9][Cb] weights, [3][Cb] derived coefficients)
-  a.noflush = T3D_ENV_SET("T3D_DEBUG_NOFLUSH") ? 1 : 0;
   // a pending BatchNorm-backward finalize of this launch's gradient coefficients is derived in the two-column kernel
   if (two_col && !a.per_sample) {
     a.fold = t3d_take_fold(a.alpha);
@@ -1149,8 +1147,7 @@ int launch_s2(Dw3BArgs& a, hipStream_t st) {
   a.rows_per_chunk = cdiv(Ho, nchunks);
   a.nchunks = cdiv(Ho, a.rows_per_chunk);
   dim3 grid;
-  static const int tb_env = getenv("T3D_DW_TB") ? atoi(getenv("T3D_DW_TB")) : 0;      // (sweep knob, tools/scratch/sweep_tb.sh)
-  const int target_blocks = tb_env ? tb_env : 512;   // (round 4 sweep, tools/scratch/sweep_tb.sh: 14x14x576 46.6 -> 41.4 us, 28x28x192 54.3 -> 51.5 against 384)
+  const int target_blocks = 512;   // (round 4 sweep: 14x14x576 46.6 -> 41.4 us, 28x28x192 54.3 -> 51.5 against 384)
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   const int nth = 256;
@@ -1177,7 +1174,6 @@ int launch_s2(Dw3BArgs& a, hipStream_t st) {
     a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
   }
   const size_t lds = (size_t)22 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64
-  a.noflush = T3D_ENV_SET("T3D_DEBUG_NOFLUSH") ? 1 : 0;
   // (in front of t3d_take_fold: a refused launch leaves the pending finalize request to the tiled fallback)
   if ((size_t)a.B * a.H * a.W * a.C * sizeof(T) >= (1ull << 31)) return T3D_ERR_UNSUPPORTED;     // 32-bit buffer offsets
   if (!a.per_sample) {

@@ -325,7 +325,7 @@ int launch_bwd(P7Args& a, int act, hipStream_t st) {
 // t3d_dwconv_fwd, k = 5, stride 1, 7x7 planes (dwconv_fwd.hip dispatches; T3D_ERR_UNSUPPORTED -> the generic kernels)
 int t3d_dw5_plane7_fwd(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats, float* gap_sum,
                        int B, int C, hipStream_t st) {
-  if ((C % 2) || (pro && pro->se) || T3D_ENV_SET("T3D_DW5_NO_PLANE")) return T3D_ERR_UNSUPPORTED;
+  if ((C % 2) || (pro && pro->se)) return T3D_ERR_UNSUPPORTED;
   P7Args a{};
   a.x = x; a.y = y; a.w = w; a.stats = stats; a.gap = gap_sum; a.gapq = g_t3d_reduce.pool_exact;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; }
@@ -340,7 +340,7 @@ int t3d_dw5_plane7_fwd(int dtype, const void* x, const t3d_prologue* pro, const 
 int t3d_dw5_plane7_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
                        const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int C,
                        hipStream_t st) {
-  if ((C % 2) || (pro && pro->se) || T3D_ENV_SET("T3D_DW5_NO_PLANE")) return T3D_ERR_UNSUPPORTED;
+  if ((C % 2) || (pro && pro->se)) return T3D_ERR_UNSUPPORTED;
   if (const int rc = t3d_fold_fallback(bb->alpha, st)) return rc;     // finished coefficients (no derive prologue here)
   P7Args a{};
   a.dz = dz; a.yraw = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;

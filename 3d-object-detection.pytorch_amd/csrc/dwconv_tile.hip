@@ -649,10 +649,10 @@ static int dw3_tile_max() {      // (read per call: the test suite flips it insi
 }
 static bool tile_shape_ok(int k, int stride, int H, int W, int C, bool pooled = false) {
   if ((C % 2) || H < 2 || W < 2) return false;
-  if (k == 5) return H >= 8 && W >= 8 && H <= (stride == 2 ? 28 : 64) && W <= (stride == 2 ? 28 : 64) && !T3D_ENV_SET("T3D_DW5_NO_TILE");
+  if (k == 5) return H >= 8 && W >= 8 && H <= (stride == 2 ? 28 : 64) && W <= (stride == 2 ? 28 : 64);
   // 3x3 forward WITH squeeze-excite pooled sums on the 14x14 stage and below: those launches go to the generic walk of
   // dwconvk_stream.hip (the 3x3 row-walk kernel has no pooled sums), which the tiles beat: 14x14x480 52 -> 36 us, x672 59 -> 51
-  if (k == 3 && pooled && stride == 1 && H <= 14 && W <= 14 && !T3D_ENV_SET("T3D_DW5_NO_TILE")) return true;
+  if (k == 3 && pooled && stride == 1 && H <= 14 && W <= 14) return true;
   if (k == 3) return H <= dw3_tile_max() && W <= dw3_tile_max();
   return false;
 }

@@ -206,12 +206,9 @@ int launch_nc(DwkArgs& a, hipStream_t st) {
   if (max_chunks < 1) max_chunks = 1;
   if (nchunks > max_chunks) nchunks = max_chunks;
   if (nchunks < 1) nchunks = 1;
-  static const int ch_env = getenv("T3D_DWK_CHUNKS") ? atoi(getenv("T3D_DWK_CHUNKS")) : 0;      // (sweep knobs)
-  if (ch_env) nchunks = ch_env;
   a.rows_per_chunk = cdiv(a.Ho, nchunks);
   a.nchunks = cdiv(a.Ho, a.rows_per_chunk);
-  static const int tb_env = getenv("T3D_DWK_TB") ? atoi(getenv("T3D_DWK_TB")) : 0;
-  const int target_blocks = tb_env ? tb_env : ((K == 5 && S == 1) ? 1024 : 768);
+  const int target_blocks = (K == 5 && S == 1) ? 1024 : 768;
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   dim3 grid;
@@ -247,12 +244,11 @@ int launch_ks(DwkArgs& a, hipStream_t st) {
   // output columns per thread, measured per layer of mobilenetv3_large at B = 256 (tools/scratch/time_dwk.py, us at NC = 1 / 2 / 4):
   //   3x3 s1 14^2 x 480 / 672 (squeeze-excite): 62.6 / 50.1 / 49.2 and 77.9 / 61.4 / 57.3;  5x5 s1 28^2 x 120: 93.7 / 105.7 / 77.8,
   //   7^2 x 960: 66.3 / 78.6 / 62.8;  5x5 s2 56^2 x 72: 93.1 / 95.3 (/ 93.8 at NC = 2), 14^2 x 672: 69.2 / 84.9 -- four columns for
-  //   stride 1, one for stride 2 (T3D_DWK_NC: sweep knob)
-  static const int env = getenv("T3D_DWK_NC") ? atoi(getenv("T3D_DWK_NC")) : 0;
-  const int nc = env ? env : (S == 1 ? 4 : 1);
-  if (nc == 1 || a.Wo < 4) return launch_nc<T, K, S, 1>(a, st);
-  if (nc == 4 && S == 1) return launch_nc<T, K, S, (S == 1 ? 4 : 2)>(a, st);
-  return launch_nc<T, K, S, 2>(a, st);
+  //   stride 1, one for stride 2
+  if constexpr (S == 1) {
+    if (a.Wo >= 4) return launch_nc<T, K, S, 4>(a, st);
+  }
+  return launch_nc<T, K, S, 1>(a, st);
 }
 
 template <typename T>

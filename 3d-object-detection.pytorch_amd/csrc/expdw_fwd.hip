@@ -308,15 +308,11 @@ __global__ __launch_bounds__(NTH) void expdw_fwd_kernel(const EdArgs a) {
 }
 
 // threads per workgroup and 16-pixel fragment groups per wave for an input width (launch_s picks the instantiation from these)
-static int expdw_nth(int W) {
-  static const int nth_env = getenv("T3D_EXPDW_NTH") ? atoi(getenv("T3D_EXPDW_NTH")) : 0;
-  return nth_env ? nth_env : (W > 60 ? 512 : 256);
-}
+static int expdw_nth(int W) { return W > 60 ? 512 : 256; }
 // input rows a workgroup can hold: the LDS budget and the per-wave fragment registers (gmax groups of 16 pixels) bound it;
 // fewer than 3 (one output row's stencil) means the shape is not served -- t3d_expdw_supported says so ahead of the launch
 static int expdw_rows(int W, int nth) {
-  static const int lds_kb_env = getenv("T3D_EXPDW_LDS_KB") ? atoi(getenv("T3D_EXPDW_LDS_KB")) : 0;
-  const int lds_kb = lds_kb_env ? lds_kb_env : (nth == 512 ? 150 : 76);
+  const int lds_kb = nth == 512 ? 150 : 76;
   const int gmax = nth == 512 ? 5 : 7;
   const size_t row_bytes = (size_t)(W + 2) * PS * 4;
   const int ir = (int)(((size_t)lds_kb << 10) / row_bytes), ir_frag = (gmax * (nth / 64) * 16) / W;

@@ -33,12 +33,7 @@ struct GemmArgs {
   // the finished block output that t3d_bn_apply would have written; the blocks of output chunk 0 also STORE it to z_out
   const void* z_res;
   void* z_out;
-  // implicit 3x3 convolution (deep-contraction kernel only; resnet.hip: t3d_conv3x3_fwd / _dgrad): the operand row of pixel m
-  // is GATHERED -- k = tap * cv.Cs + c reads channel c of the source pixel that tap (ky, kx) pairs with destination pixel m --
-  // instead of read from a patch matrix in HBM.  mode 1 (forward): source = destination * stride - 1 + (ky, kx); mode 2 (data
-  // gradient): source = (destination + 1 - (ky, kx)) / stride where that divides.  Out-of-range taps contribute zero AFTER
-  // the operand transform (the convolution pads the activated tensor; the BatchNorm-backward affine has a constant term).
-  struct Conv3 { int mode, Dh, Dw, Sh, Sw, Cs, lgCs, stride; } cv;
+  int unused_[8];        // (where the implicit-3x3 gather's fields were: the kernels' argument layout, and so their code, stay as measured)
   int wfrag;             // `w` is the fragment-order copy (include/t3d.h: T3D_W_FRAG; streaming and deep-contraction kernels)
   T3dQuant quant;        // forward BatchNorm sums snapped onto a fixed grid (order-independent, common.h); q == 0: off
 };
@@ -62,10 +57,6 @@ int stream_launch(GemmArgs& a, hipStream_t st);
 // from L2); returns T3D_ERR_UNSUPPORTED for every other shape.  deep_shape: the shapes it takes (t3d_pwconv_wants_frag)
 int deep_launch(GemmArgs& a, hipStream_t st);
 bool deep_shape(int Kin, int Nout);
-// bf16 materialising forward of shallow contractions with wide outputs on the small planes (pwconv_wide.hip: operand staged once,
-// all output channels per workgroup); T3D_ERR_UNSUPPORTED for every other launch.  wide_shape: layers whose fragment-order copy it wants
-int wide_launch(GemmArgs& a, hipStream_t st);
-bool wide_shape(int Kin, int Nout);
 // the same kernel in fp16 storage, inference forward only (pwconv_stream_f16.hip)
 int stream_launch_f16(GemmArgs& a, hipStream_t st);
 // fp32 storage, inference forward of many-pixel layers (pwconv_f32_reg.hip); T3D_ERR_UNSUPPORTED for everything else

@@ -56,8 +56,7 @@ __device__ unsigned long long g_deep_trace[16];
 constexpr int RT = 4;        // row tiles (16 pixels) per block
 constexpr int NW = 8;        // waves per block: two per SIMD (round 5; one per SIMD with the whole register file before)
 
-// CV: implicit 3x3 convolution (GemmArgs::cv) -- a compile-time variant: the plain kernel's phase loop stays branch-free
-template <bool DG, bool CV, int NTW, int KSP>
+template <bool DG, int NTW, int KSP>
 __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, const int KS, const int ntiles, const int nrep,
                                                              const long long rstride) {
   // NTW 16-row tiles per wave (tiles wave, wave + 8, .. of the chunk: <= 8 NTW tiles), KSP k-steps per phase (one LDS buffer = RT KSP KB);
@@ -109,48 +108,12 @@ __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, cons
   const int mrow = min(m0 + srt * 16 + lc, a.M - 1);
   const size_t arow = (size_t)mrow * a.Kin + lg * 8;
   const bool rok = m0 + srt * 16 + lc < a.M;
-  // implicit 3x3 convolution (pwconv_common.h: Conv3): this lane's destination pixel, once
-  constexpr bool cv = CV;
-  int cvb = 0, cvy = 0, cvx = 0;
-  if constexpr (cv) {
-    cvx = mrow % a.cv.Dw;
-    const int t = mrow / a.cv.Dw;
-    cvy = t % a.cv.Dh;
-    cvb = t / a.cv.Dh;
-  }
-  // k-step ks (wave-uniform) -> element offset of the lane's 8 operand channels in the source tensor, or -1: the tap falls
-  // outside the source (zero after the transform)
-  auto cv_off = [&](const int ks) -> long long {
-    const int k0 = min(ks * 32, a.Kin - 32);
-    const int tap = k0 >> a.cv.lgCs, c = k0 & (a.cv.Cs - 1);
-    const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;             // tap / 3, tap % 3 for tap <= 8
-    int sy, sx;
-    bool ok;
-    if (a.cv.mode == 1) {
-      sy = cvy * a.cv.stride - 1 + ky;
-      sx = cvx * a.cv.stride - 1 + kx;
-      ok = true;
-    } else {
-      const int ty = cvy + 1 - ky, tx = cvx + 1 - kx, sm = a.cv.stride - 1;       // stride 1 or 2
-      ok = ((ty | tx) & sm) == 0;
-      sy = ty >> sm;
-      sx = tx >> sm;
-    }
-    ok = ok && (unsigned)sy < (unsigned)a.cv.Sh && (unsigned)sx < (unsigned)a.cv.Sw;
-    return ok ? ((long long)(cvb * a.cv.Sh + sy) * a.cv.Sw + sx) * a.cv.Cs + c + lg * 8 : -1;
-  };
   bf16x8 pa[2][IT], pb[DG ? 2 : 1][DG ? IT : 1];
   auto a_issue = [&](auto slot_tag, const int ph) {
     constexpr int SL = decltype(slot_tag)::value;
 #pragma unroll
     for (int j = 0; j < IT; ++j) {
-      size_t o;
-      if constexpr (cv) {
-        const long long g = cv_off(ph * KSP + sks + j);
-        o = g < 0 ? (size_t)lg * 8 : (size_t)g;                 // (an out-of-range tap reads a valid address; zeroed later)
-      } else {
-        o = arow + min((ph * KSP + sks + j) * 32, a.Kin - 8 - lg * 8);
-      }
+      const size_t o = arow + min((ph * KSP + sks + j) * 32, a.Kin - 8 - lg * 8);
       pa[SL][j] = *reinterpret_cast<const bf16x8*>(A0 + o);
       if (DG) pb[DG ? SL : 0][DG ? j : 0] = *reinterpret_cast<const bf16x8*>(A1 + o);
     }
@@ -167,32 +130,21 @@ __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, cons
     ecoef[i] = v ? a.e_scale[n] : 1.f;
     ecoef[BN + i] = v ? a.e_shift[n] : 0.f;
   }
-  // (implicit 3x3 convolution: the coefficients are per SOURCE channel, Cs of them, repeated for each of the nine taps)
-  const int ncoef = cv ? a.cv.Cs : a.Kin;
   if (a.fold) {
     for (int i = a.Kin + tid; i < kpad; i += 64 * NW) {
       coef[i] = DG ? 0.f : 1.f; coef[kpad + i] = 0.f; coef[2 * kpad + i] = 0.f;
     }
-    t3d_fold_block(a.fold, 0, ncoef, coef, kpad, blockIdx.x == 0 && blockIdx.y == 0);
-    if constexpr (cv) {
-      for (int i = ncoef + tid; i < a.Kin; i += 64 * NW) {
-        const int c = i & (ncoef - 1);
-        coef[i] = coef[c]; coef[kpad + i] = coef[kpad + c];
-        if (DG) coef[2 * kpad + i] = coef[2 * kpad + c];
-      }
-      __syncthreads();
-    }
+    t3d_fold_block(a.fold, 0, a.Kin, coef, kpad, blockIdx.x == 0 && blockIdx.y == 0);
   } else {
     for (int i = tid; i < kpad; i += 64 * NW) {
       const bool v = i < a.Kin;
-      const int c = cv ? (i & (ncoef - 1)) : i;
       if (!DG) {
-        coef[i] = (v && a.p0) ? a.p0[c] : 1.f;
-        coef[kpad + i] = (v && a.p0) ? a.p1[c] : 0.f;
+        coef[i] = (v && a.p0) ? a.p0[i] : 1.f;
+        coef[kpad + i] = (v && a.p0) ? a.p1[i] : 0.f;
       } else {
-        coef[i] = v ? a.p0[c] : 0.f;
-        coef[kpad + i] = v ? a.p1[c] : 0.f;
-        coef[2 * kpad + i] = v ? a.p2[c] : 0.f;
+        coef[i] = v ? a.p0[i] : 0.f;
+        coef[kpad + i] = v ? a.p1[i] : 0.f;
+        coef[2 * kpad + i] = v ? a.p2[i] : 0.f;
       }
     }
     __syncthreads();
@@ -220,8 +172,7 @@ __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, cons
 #pragma unroll
     for (int j = 0; j < IT; ++j) {
       const int k = (ph * KSP + sks + j) * 32 + lg * 8;
-      bool ok = rok && (k < a.Kin);
-      if constexpr (cv) ok = ok && cv_off(ph * KSP + sks + j) >= 0;
+      const bool ok = rok && (k < a.Kin);
       const int kc = min(k, kpad - 8);
       const float4 c0a = *reinterpret_cast<const float4*>(coef + kc), c0b = *reinterpret_cast<const float4*>(coef + kc + 4);
       const float4 c1a = *reinterpret_cast<const float4*>(coef + kpad + kc),
@@ -368,15 +319,15 @@ __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, cons
   DEEP_STAMP(5);
 }
 
-template <bool DG, bool CV, int NTW, int KSP>
+template <bool DG, int NTW, int KSP>
 int launch_deep(GemmArgs& a, int KS, int ntiles, int nchunks, hipStream_t st) {
   const size_t lds = (size_t)2 * RT * KSP * 1024 + (size_t)3 * KS * 32 * 4 + (size_t)ntiles * 16 * (2 * 4 + 2 * 8);
   if (lds > 150 * 1024) return T3D_ERR_UNSUPPORTED;
-  const void* fn = (const void*)pw_deep_kernel<DG, CV, NTW, KSP>;
+  const void* fn = (const void*)pw_deep_kernel<DG, NTW, KSP>;
   if (lds > 64 * 1024) (void)t3d_max_lds(fn, (int)lds);
   a.quant = (!DG && a.stats && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for(a.M) : T3dQuant{0.0, 0.0};
   a.fold = t3d_take_fold(a.p0);
-  T3D_LAUNCH_TIMED((pw_deep_kernel<DG, CV, NTW, KSP>), dim3(cdiv(a.M, 16 * RT), nchunks), dim3(64 * NW), lds, st, a, KS, ntiles,
+  T3D_LAUNCH_TIMED((pw_deep_kernel<DG, NTW, KSP>), dim3(cdiv(a.M, 16 * RT), nchunks), dim3(64 * NW), lds, st, a, KS, ntiles,
                      g_t3d_reduce.nrep, g_t3d_reduce.stats_stride);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
@@ -419,26 +370,14 @@ int deep_launch(GemmArgs& a, hipStream_t st) {
   if (a.a2 || a.z_out || a.per_sample || a.ps_stats || a.e_se || a.bias || (!a.dgrad && a.p2)) return T3D_ERR_UNSUPPORTED;
   if (a.row0 && a.row0 != a.Kin) return T3D_ERR_UNSUPPORTED;
   if (a.dgrad && (!a.a1 || !a.p0 || !a.p1 || !a.p2)) return T3D_ERR_UNSUPPORTED;
-  if (!a.cv.mode && !deep_shape(a.Kin, a.Nout)) return T3D_ERR_UNSUPPORTED;
-  if (a.cv.mode && (a.Kin != 9 * a.cv.Cs || (a.cv.Cs & (a.cv.Cs - 1)) || a.cv.Cs < 32 || (a.cv.stride != 1 && a.cv.stride != 2)))
-    return T3D_ERR_UNSUPPORTED;
+  if (!deep_shape(a.Kin, a.Nout)) return T3D_ERR_UNSUPPORTED;
   const int KS = cdiv(a.Kin, 32);
   const int pairs = cdiv(a.Nout, 32);
-  // Two shapes of a wave's share (measured, tools/scratch/deep_rot_ab.sh): 2 tiles x 4 k-steps of weights ahead (chunks of <= 16
-  // tiles = 256 channels), or 3 tiles x 2 k-steps (<= 24 tiles = 384 channels) where that makes ONE chunk of two -- every chunk stages AND
-  // transforms the operand again: 960 -> 320 @7x7 35.2 us as two chunks of 10 tiles, 23.5 as one of 20; 320 <- 1280 59.4 / 39.1;
-  // 960 -> 160 (one chunk either way) 18.3 / 20.9.  Chunks evenly sized.
-  // OPT-IN (T3D_DEEP_WIDE=1): alone the two launches it changes get 12 and 20 us faster, the STEP does not (6.718 / 6.694 / 6.700
-  // ms with against 6.698 / 6.669 / 6.680 without, three same-box pairs) -- finding 20's lesson once more
-  const bool wide = pairs > 8 && pairs <= 12 && T3D_ENV_SET("T3D_DEEP_WIDE");        // (one chunk instead of two; 32 pairs as 3 x 22 tiles ran 53 us, as 4 x 16 45)
-  const int per = wide ? 12 : 8;
-  const int nchunks = cdiv(pairs, per), ntiles = 2 * cdiv(pairs, nchunks);
-  if (wide) {
-    if (a.cv.mode) return a.dgrad ? launch_deep<true, true, 3, 2>(a, KS, ntiles, nchunks, st) : launch_deep<false, true, 3, 2>(a, KS, ntiles, nchunks, st);
-    return a.dgrad ? launch_deep<true, false, 3, 2>(a, KS, ntiles, nchunks, st) : launch_deep<false, false, 3, 2>(a, KS, ntiles, nchunks, st);
-  }
-  if (a.cv.mode) return a.dgrad ? launch_deep<true, true, 2, 4>(a, KS, ntiles, nchunks, st) : launch_deep<false, true, 2, 4>(a, KS, ntiles, nchunks, st);
-  return a.dgrad ? launch_deep<true, false, 2, 4>(a, KS, ntiles, nchunks, st) : launch_deep<false, false, 2, 4>(a, KS, ntiles, nchunks, st);
+  // a wave's share: 2 tiles x 4 k-steps of weights ahead, chunks of <= 16 tiles = 256 channels, evenly sized (every chunk stages
+  // AND transforms the operand again).  (3 tiles x 2 k-steps in ONE chunk of <= 24 tiles: the two launches it changes get 12 and
+  // 20 us faster alone, the STEP does not -- finding 20's lesson once more; code removed, see git history)
+  const int nchunks = cdiv(pairs, 8), ntiles = 2 * cdiv(pairs, nchunks);
+  return a.dgrad ? launch_deep<true, 2, 4>(a, KS, ntiles, nchunks, st) : launch_deep<false, 2, 4>(a, KS, ntiles, nchunks, st);
 }
 
 }  // namespace t3d_pw
@@ -452,7 +391,7 @@ extern "C" int t3d_pwconv_frag_bytes(int rows, int cols) {
 // where the fragment-order copy PAYS: the deep-contraction kernel's shapes.  (The streaming kernel takes the layout for every
 // shape of its own -- its weight staging becomes one linear copy -- but that is worth ~1 us per launch alone and nothing in
 // the step, less than packing a second copy of every layer costs: DESIGN finding 34.)
-extern "C" int t3d_pwconv_wants_frag(int K, int N) { return (t3d_pw::deep_shape(K, N) || t3d_pw::wide_shape(K, N)) ? 1 : 0; }
+extern "C" int t3d_pwconv_wants_frag(int K, int N) { return t3d_pw::deep_shape(K, N) ? 1 : 0; }
 
 extern "C" int t3d_pwconv_pack_frag(const void* w, void* out, int rows, int cols, void* stream) {
   if (!w || !out || rows <= 0 || cols <= 0) return T3D_ERR_ARG;

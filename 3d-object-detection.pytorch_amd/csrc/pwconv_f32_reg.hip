@@ -291,16 +291,16 @@ int launch_reg_nt(GemmArgs& a, int NT, hipStream_t st) {
 // fp32 storage, inference forward; T3D_ERR_UNSUPPORTED = "not a launch for this kernel" (pwconv.hip takes it)
 int f32_reg_launch(GemmArgs& a, hipStream_t st) {
   if (a.dgrad) {
-    if (!a.a1 || !a.p0 || !a.p1 || !a.p2 || a.per_sample || a.ps_stats || a.e_se || a.a2 || a.cv.mode || a.fold || a.kz > 1 ||
+    if (!a.a1 || !a.p0 || !a.p1 || !a.p2 || a.per_sample || a.ps_stats || a.e_se || a.a2 || a.fold || a.kz > 1 ||
         a.wfrag || a.bias || a.z_out || a.z_res || !a.out)
       return T3D_ERR_UNSUPPORTED;
   } else
-  if (a.ps_stats || (a.p2 && a.z_out) || a.a1 || a.a2 || a.cv.mode || a.fold || a.per_sample || a.e_se || a.kz > 1 ||
+  if (a.ps_stats || (a.p2 && a.z_out) || a.a1 || a.a2 || a.fold || a.per_sample || a.e_se || a.kz > 1 ||
       a.wfrag || (a.z_res && !a.z_out) || (a.z_out && (a.act != T3D_ACT_NONE || a.bias)) ||
       (a.stats && !a.out))
     return T3D_ERR_UNSUPPORTED;
   if ((a.Kin % 8) || (a.Nout % 8) || a.M < 1024) return T3D_ERR_UNSUPPORTED;      // (few-pixel layers: the split-contraction path)
-  // Task shape (tools/time_pw_f32.py --sweep): output tiles per wave = the count that pads the layer's tiles least, 5 and 4
+  // Task shape (round-5 sweep): output tiles per wave = the count that pads the layer's tiles least, 5 and 4
   // before 6 (4 x 6 takes 224 registers) before 3; 4 pixel groups per wave unless that leaves fewer than 128 workgroups (7x7 x
   // 256 = 784 groups x 10 tiles as 4 x 5 would be 98), then 2
   const int tiles = cdiv(a.Nout, 16), G = cdiv(a.M, 16);
@@ -310,8 +310,7 @@ int f32_reg_launch(GemmArgs& a, hipStream_t st) {
     for (int c : {5, 4, 6, 3})
       if (cdiv(tiles, c) * c < pad) { pad = cdiv(tiles, c) * c; NT = c; }
   }
-  int R = (long long)cdiv(cdiv(G, 4), 4) * cdiv(tiles, NT) >= 128 ? 4 : 2;
-  if (const char* e = getenv("T3D_F32_SHAPE")) { R = e[0] - '0'; NT = e[1] - '0'; }    // (sweep knob)
+  const int R = (long long)cdiv(cdiv(G, 4), 4) * cdiv(tiles, NT) >= 128 ? 4 : 2;
   return R == 4 ? launch_reg_nt<4>(a, NT, st) : launch_reg_nt<2>(a, NT, st);
 }
 

@@ -599,7 +599,7 @@ int launch_v(GemmArgs& a, int KS, hipStream_t st) {
   if (per_cu > by_lds) per_cu = by_lds;
   if (per_cu < 1) per_cu = 1;
   int nxb = (256 * per_cu) / nchunks;
-  a.ps_wave = (ps && gps <= 16 && !T3D_ENV_SET("T3D_PW_PS_BLOCK")) ? 1 : 0;
+  a.ps_wave = (ps && gps <= 16) ? 1 : 0;
   const int need = ps ? (a.ps_wave ? cdiv(a.M / a.HW, threads / 64) : a.M / a.HW) : cdiv(ngroups, threads / 64);
   if (nxb > need) nxb = need;
   if (nxb < 1) nxb = 1;

@@ -78,10 +78,7 @@ struct WgtArgs {
   double* stats;          // [2][K] replicas or null
   int nrep;
   long long rstride;
-  // implicit 3x3 convolution (conv3x3.hip): the a side [M][K = 9 C] is not a patch matrix in memory -- column k = tap * C + c
-  // of output pixel m reads channel c of input pixel (oy * stride - 1 + ky, ox * stride - 1 + kx) of x [B][H][W][C] (raw, the
-  // BatchNorm + activation prologue per channel c), zero outside the image
-  struct { int on, H, W, Ho, Wo, C, lgC, stride; unsigned mulW, mulH; } cv;
+  int unused_[10];        // (where the implicit-3x3 gather's fields were: the kernels' argument layout, and so their code, stay as measured)
   int assign;             // dw is WRITTEN, not accumulated into (the y-free product matrix: no clear needed ahead of the launch)
   // squeeze-excite gate of the a side staged in LDS (GEN, `se` set): gs_ns = samples a block's pixel range can touch (0: the
   // gates are read from global memory per staged vector, round 3's path), mulHW = ceil(2^32 / HW) for (m - first sample's
@@ -114,8 +111,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int rs, int ch0, i
 // read as they lie (pixel-major, 8 consecutive virtual channels per lane), D[k][pixel] -> a lane holds 4 consecutive
 // channels of one pixel: 8-byte stores; the skip gradient and the raw tensor of the producer (BatchNorm-backward sums of x's
 // producer, exactly as in the streaming kernel's epilogue) are fetched with the step's operands.
-// CV: implicit 3x3 convolution on the a side (WgtArgs::cv) -- a compile-time variant, the plain kernels' staging is untouched
-template <int NTPW, int NTQ, bool SWAP, int G, int D, int GEN, bool YF, int SK = 1, bool DGF = false, bool CV = false>
+template <int NTPW, int NTQ, bool SWAP, int G, int D, int GEN, bool YF, int SK = 1, bool DGF = false>
 __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
   static_assert(!DGF || (YF && !SWAP), "the fused data gradient exists for the y-free layout only");
   constexpr int PB = 64 * NTPW, QB = 16 * NTQ;
@@ -177,9 +173,8 @@ __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
   for (int i = threadIdx.x; i < aB; i += 256 * G) {
     const int k = a0c + i;
     const bool v = k < a.K;
-    const int kc = CV ? (k & (a.cv.C - 1)) : k;
-    ca[i] = ((v && a.scale) ? a.scale[kc] : 1.f) * (c6 ? T3D_SIXTH : 1.f);
-    ca[aB + i] = ((v && a.scale) ? a.shift[kc] : 0.f) * (c6 ? T3D_SIXTH : 1.f);
+    ca[i] = ((v && a.scale) ? a.scale[k] : 1.f) * (c6 ? T3D_SIXTH : 1.f);
+    ca[aB + i] = ((v && a.scale) ? a.shift[k] : 0.f) * (c6 ? T3D_SIXTH : 1.f);
   }
   float* const gsl = coef + ((NCOEF + 3) & ~3);           // GEN: [gs_ns][aB] gate slice of this block's samples and channels
   const int gs_b0 = GEN ? mbeg / a.HW : 0;
@@ -297,9 +292,8 @@ __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
   // DGF units of a step: (16-pixel tile, 16-channel tile) pairs, dealt round-robin to the pipeline's four waves
   constexpr int NU = DGF ? (STEP / 16) * NTQ : 1, UPW = (NU + 3) / 4;
   struct Epi { bf16x4 res[UPW], xr[UPW]; };
-  struct NoMask {};
-  // okm (implicit 3x3 only): bit i = vector i's tap is inside the image
-  struct Regs { bf16x8 rz[VDY], ry[VDY], rx[VA]; Epi e; typename std::conditional<CV, unsigned, NoMask>::type okm; };
+  struct NoMask {};        // (an empty member: without it two SK = 2 instances allocate their registers differently)
+  struct Regs { bf16x8 rz[VDY], ry[VDY], rx[VA]; Epi e; NoMask okm; };
   Regs rr[D];
   Epi ecur;                     // epilogue operands of the step that is in LDS now
   const int lgq = lane >> 4, lcq = lane & 15;
@@ -324,24 +318,11 @@ __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
         R.ry[i] = *reinterpret_cast<const bf16x8*>(yy + (size_t)m * a.N + n);
       }
     }
-    if constexpr (CV) R.okm = ~0u;
 #pragma unroll
     for (int i = 0; i < VA; ++i) {
       const int v = min(tid + 256 * i, nav - 1);
       const int row = v / aV, k = min(a0c + (v % aV) * 8, a.K - 8), m = min(m0 + row, a.M - 1);
-      if constexpr (CV) {
-        const int tap = k >> a.cv.lgC, c = k & (a.cv.C - 1);
-        const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
-        const int t = (int)__umulhi((unsigned)m, a.cv.mulW), ox = m - t * a.cv.Wo;       // m / Wo, m % Wo (exact: launcher)
-        const int b = (int)__umulhi((unsigned)t, a.cv.mulH), oy = t - b * a.cv.Ho;
-        const int iy = oy * a.cv.stride - 1 + ky, ix = ox * a.cv.stride - 1 + kx;
-        const bool ok = (unsigned)iy < (unsigned)a.cv.H && (unsigned)ix < (unsigned)a.cv.W;
-        const size_t o = ok ? ((size_t)(b * a.cv.H + iy) * a.cv.W + ix) * a.cv.C + c : 0;
-        R.rx[i] = *reinterpret_cast<const bf16x8*>(xx + o);
-        if (!ok) R.okm &= ~(1u << i);
-      } else {
-        R.rx[i] = *reinterpret_cast<const bf16x8*>(xx + (size_t)m * a.K + k);
-      }
+      R.rx[i] = *reinterpret_cast<const bf16x8*>(xx + (size_t)m * a.K + k);
     }
     if constexpr (DGF) {
 #pragma unroll
@@ -409,8 +390,7 @@ __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
       const int v = tid + 256 * i;
       if (v < nav) {
         const int row = v / aV, cl = (v % aV) * 8, m = m0 + row;
-        bool ok = m < mend && a0c + cl < a.K;
-        if constexpr (CV) ok = ok && ((R.okm >> i) & 1u);
+        const bool ok = m < mend && a0c + cl < a.K;
         bf16x8 o = rx[i];
         if (!plain_a) {
           float u[8], sc[8], sh[8];
@@ -713,7 +693,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_tr_kernel(const float* __res
   }
 }
 
-template <int NTPW, int NTQ, bool SWAP, int D, int GEN, bool YF = false, int SK = 1, bool CV = false>
+template <int NTPW, int NTQ, bool SWAP, int D, int GEN, bool YF = false, int SK = 1>
 int launch_d(WgtArgs& a, hipStream_t st) {
   constexpr int G = 2;
   constexpr int STEP = 32 * SK;
@@ -725,14 +705,13 @@ int launch_d(WgtArgs& a, hipStream_t st) {
   const int dyB = a.swap ? QB : PB, aB = a.swap ? PB : QB;
   size_t lds = (size_t)G * 2 * STEP * ((PB + 8) + (QB + 8)) * 2 + (size_t)(3 * dyB + 2 * aB) * 4;
   // pixel splits: fill the chip (2 blocks per CU), but keep the partial-dW flush (S * N*K atomics) below ~8 MB
-  static const int tgt_env = getenv("T3D_WG_TGT_BLOCKS") ? atoi(getenv("T3D_WG_TGT_BLOCKS")) : 0;      // (sweep knob)
   // (256 = one 512-thread workgroup per CU.  Round 6 sweeps, same box: 128 / 192 / 384 / 512 for every layer 7.08 / 6.93 / 6.98 / 7.07
   // against 6.80-6.91 ms per step; 64 / 128 / 192 for the <= 14x14 layers only 7.11 / 7.02 / 6.93 against 6.89-6.90)
-  const int tgt_blocks = tgt_env ? tgt_env : 256;
+  const int tgt_blocks = 256;
   const long long cap_mb = 8;
   int S = (tgt_blocks + tiles - 1) / tiles;
   const long long tile_bytes = (long long)tiles * PB * QB * 4;
-  const bool use_ws = g_t3d_ws.ptr && g_t3d_ws.bytes >= tile_bytes && !T3D_ENV_SET("T3D_WG_ATOMIC");
+  const bool use_ws = g_t3d_ws.ptr && g_t3d_ws.bytes >= tile_bytes;
   if (use_ws) {
     const long long fit = g_t3d_ws.bytes / tile_bytes;   // partial sets the workspace holds
     if (S > fit) S = (int)fit;
@@ -759,9 +738,9 @@ int launch_d(WgtArgs& a, hipStream_t st) {
   // (atomics into dw: an assigned-to dw is cleared first; with partial tiles the reduction writes it)
   if (a.assign && !use_ws && hipMemsetAsync(a.dw, 0, (size_t)a.N * a.K * sizeof(float), st) != hipSuccess) return T3D_ERR_LAUNCH;
   if (lds > 64 * 1024)
-    (void)t3d_max_lds((const void*)pw_wgrad_tr_kernel<NTPW, NTQ, SWAP, G, D, GEN, YF, SK, false, CV>, (int)lds);
+    (void)t3d_max_lds((const void*)pw_wgrad_tr_kernel<NTPW, NTQ, SWAP, G, D, GEN, YF, SK, false>, (int)lds);
   a.nsplit = S;
-  T3D_LAUNCH_TIMED((pw_wgrad_tr_kernel<NTPW, NTQ, SWAP, G, D, GEN, YF, SK, false, CV>), dim3(tiles * S), dim3(256 * G), lds, st, a);
+  T3D_LAUNCH_TIMED((pw_wgrad_tr_kernel<NTPW, NTQ, SWAP, G, D, GEN, YF, SK, false>), dim3(tiles * S), dim3(256 * G), lds, st, a);
   if (use_ws) {
     // split groups inside the workgroup: enough parallelism for a small dW with hundreds of splits
 #define T3D_WGR(SPV)                                                                                                              \
@@ -785,10 +764,6 @@ int launch_d(WgtArgs& a, hipStream_t st) {
 template <int NTPW, int NTQ, bool SWAP>
 int launch_sw(WgtArgs& a, hipStream_t st) {
   const int depth = 2;   // 2 measured best (1: -12 %, 3: -2 %)
-  if (a.cv.on) {          // implicit 3x3 convolution: K = 9 C > N, i.e. the swapped orientation, wide tiles only
-    if constexpr (SWAP && NTQ >= 4) return launch_d<NTPW, NTQ, true, 2, false, false, 1, true>(a, st);
-    else return T3D_ERR_UNSUPPORTED;
-  }
   if (a.yfree) {
     if constexpr (!SWAP) {
       const int sk_env = 0;
@@ -805,7 +780,7 @@ int launch_sw(WgtArgs& a, hipStream_t st) {
   // plain kernel (the per-vector global gate reads of round 3 forced depth 1: two exposed round trips per 32-pixel step)
   // (GEN = 1, round 3's path, keeps them as global reads inside the staging step -- and every conditional global load there makes
   // the compiler drain ALL outstanding loads, the next steps' operands included: 2x the plain kernel's duration, isolated)
-  if (a.per_sample || (a.se && T3D_ENV_SET("T3D_WG_GATE_GLOBAL"))) return launch_d<NTPW, NTQ, SWAP, 1, 1>(a, st);
+  if (a.per_sample) return launch_d<NTPW, NTQ, SWAP, 1, 1>(a, st);
   if (a.se) return launch_d<NTPW, NTQ, SWAP, 2, 2>(a, st);
   if (depth == 1) return launch_d<NTPW, NTQ, SWAP, 1, false>(a, st);
   // pixels per step (see the kernel): wider steps for the narrow tiles of the layers with many pixels per workgroup
@@ -835,8 +810,7 @@ static int choose_and_launch(WgtArgs& a, hipStream_t st) {
   // every pipeline >= ~12 steps of 32 pixels when the chip is filled -- a wide tile reads each operand once but, on the
   // small-pixel-count layers, degenerates into a handful of steps followed by a large partial flush; a narrow tile
   // re-reads the (small) Q-side operand through L2 instead.
-  static const int min_steps_env = getenv("T3D_WG_MIN_STEPS") ? atoi(getenv("T3D_WG_MIN_STEPS")) : 0;      // (sweep knob)
-  const int min_steps = min_steps_env ? min_steps_env : 12;
+  const int min_steps = 12;
   auto steps_with = [&](int ntpw, int qb) {
     const int tiles = cdiv(P, 64 * ntpw) * cdiv(Q, qb);
     int S = cdiv(256, tiles);
@@ -852,17 +826,17 @@ static int choose_and_launch(WgtArgs& a, hipStream_t st) {
   }
   if (Q <= 64) {
     // (six row tiles per wave spill outside the y-free layout -- 76-344 B of scratch at 256 registers: ResNet-50's 256 -> 64
-    // bottleneck entries 223 / 118 us per launch, 12.0 -> 11.4 ms per step without it; T3D_WG_6X4=1 restores it)
-    if (P > 192 && steps_with(6, 64) >= min_steps && (a.yfree || T3D_ENV_SET("T3D_WG_6X4"))) return launch_cfg<6, 4>(a, st);
+    // bottleneck entries 223 / 118 us per launch, 12.0 -> 11.4 ms per step without it)
+    if (P > 192 && steps_with(6, 64) >= min_steps && a.yfree) return launch_cfg<6, 4>(a, st);
     if (P > 64 && steps_with(3, 64) >= min_steps) return launch_cfg<3, 4>(a, st);
     return launch_cfg<1, 4>(a, st);
   }
   // (round 6 sweep, isolated, B = 256 at 14x14: 576 -> 96 55 -> 34 us and 384 -> 96 39 -> 30 us with the wide tile from 5 steps on;
   // 480 -> 112 40 -> 36 us from 8; the 64- and 160-column tiles keep 12: 384 -> 64 and 320 -> 1280 lose below it)
-  if (Q <= 96) return (P > 64 && steps_with(3, 96) >= (min_steps_env ? min_steps : 5)) ? launch_cfg<3, 6>(a, st) : launch_cfg<1, 6>(a, st);
+  if (Q <= 96) return (P > 64 && steps_with(3, 96) >= 5) ? launch_cfg<3, 6>(a, st) : launch_cfg<1, 6>(a, st);
   // 112 channels on the narrow side (MobileNetV3-large's 14x14 stage, 480 / 672 -> 112): seven column tiles -- the ten-tile kernel
   // multiplied 30 % padding and, at three row tiles per wave, spilled (256 registers + 200-460 B of scratch)
-  if (Q <= 112) return (P > 64 && steps_with(3, 112) >= (min_steps_env ? min_steps : 8)) ? launch_cfg<3, 7>(a, st) : launch_cfg<1, 7>(a, st);
+  if (Q <= 112) return (P > 64 && steps_with(3, 112) >= 8) ? launch_cfg<3, 7>(a, st) : launch_cfg<1, 7>(a, st);
   // 128 / 256 / 512 ... channels on the narrow side (ResNet-50's bottlenecks): eight column tiles, no padding -- ten multiplied
   // 25 % zeros there and spilled at three row tiles per wave
   if (Q % 128 == 0) return (P > 64 && steps_with(3, 128) >= min_steps) ? launch_cfg<3, 8>(a, st) : launch_cfg<1, 8>(a, st);
@@ -897,27 +871,6 @@ int t3d_pw_wgrad_tr_entry(const void* dz, const void* y, const t3d_bnbwd* bb, co
   return choose_and_launch(a, st);
 }
 
-// implicit 3x3 convolution weight gradient (conv3x3.hip): dw [N][9 C] (patch-column order) += dy^T * gathered act(x)
-int t3d_pw_wgrad_tr_conv3(const void* dz, const void* y, const t3d_bnbwd* bb, const void* x, const t3d_prologue* pro, float* dw,
-                          int B, int H, int W, int C, int N, int stride, hipStream_t st) {
-  WgtArgs a{};
-  a.dz = dz; a.y = y; a.x = x;
-  a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma;
-  if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-  a.dw = dw; a.M = B * Ho * Wo; a.HW = Ho * Wo; a.K = 9 * C; a.N = N;
-  int lg = 0;
-  while ((1 << lg) < C) ++lg;
-  // m / Wo and (m / Wo) / Ho as __umulhi(n, ceil(2^32 / d)): exact while n < 2^32 / d
-  if ((unsigned long long)a.M * (unsigned)(Wo > Ho ? Wo : Ho) >= (1ull << 32)) return T3D_ERR_UNSUPPORTED;
-  a.cv.on = 1; a.cv.H = H; a.cv.W = W; a.cv.Ho = Ho; a.cv.Wo = Wo; a.cv.C = C; a.cv.lgC = lg; a.cv.stride = stride;
-  a.cv.mulW = (unsigned)(((1ull << 32) + Wo - 1) / Wo);
-  a.cv.mulH = (unsigned)(((1ull << 32) + Ho - 1) / Ho);
-  a.fold = t3d_take_fold(a.alpha);
-  a.assign = 1;          // dw_packed is written (by the partial-tile reduction, or cleared first): the caller need not zero it
-  return choose_and_launch(a, st);
-}
-
 // ---- fused y-free backward (pwconv_yfree.hip: t3d_pwconv_bwd_yfree / _finish) ------------------------------------------
 // one configuration per layer shape, shared by the launch and by the later reduction of its partial tiles
 struct YfCfg { int ntpw, ntq, sk, S, rows_per_split, PB, QB; };
@@ -928,11 +881,10 @@ static bool yf_cfg(int M, int K, int N, YfCfg& c) {
   if (K > 32 || P > 256 || P <= 64) return false;
   c.ntq = K <= 16 ? 1 : 2;
   c.ntpw = P <= 128 ? 2 : (P <= 192 ? 3 : 4);
-  static const int sk_m_env = getenv("T3D_YF_SK_M") ? atoi(getenv("T3D_YF_SK_M")) : 0, s_env = getenv("T3D_YF_S") ? atoi(getenv("T3D_YF_S")) : 0;   // (sweep knobs)
-  c.sk = M >= (sk_m_env ? sk_m_env : (1 << 20)) ? 2 : 1;
+  c.sk = M >= (1 << 20) ? 2 : 1;
   c.PB = 64 * c.ntpw; c.QB = 16 * c.ntq;
   const int step = 32 * c.sk;
-  int S = s_env ? s_env : 256;
+  int S = 256;
   const int maxs = cdiv(M, step * 4 * 2);
   if (S > maxs) S = maxs;
   if (S < 1) S = 1;

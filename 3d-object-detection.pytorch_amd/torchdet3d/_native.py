@@ -86,8 +86,6 @@ SIGNATURES = {
     't3d_subsample': [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     't3d_ir_block_eval': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     't3d_bn_apply': [_I, _P, _PP, _P, _P, _I, _I, _P],
-    't3d_bn_apply_gram': [_I, _P, _PP, _P, _P, _P, _I, _I, _P],
-    't3d_gram_bn_finalize': [_P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P],
     't3d_bn_act_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _P],
     't3d_gap_fwd': [_I, _P, _PP, _P, _I, _I, _I, _P],
     't3d_gap_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _I, _P],
@@ -127,10 +125,6 @@ SIGNATURES = {
     't3d_metrics_per_sample': [_P, _P, _P, _P, _P, _I, _I, _P],
     't3d_expdw_fwd': [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     't3d_expdw_supported': [_I, _I, _I, _I, _I, _I, _I, _I],
-    't3d_conv3x3_fwd': [_I, _P, _PP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_conv3x3_dgrad': [_I, _P, _P, _BP, _P, _P, _PP, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_conv3x3_wgrad': [_I, _P, _P, _BP, _P, _PP, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_pack_conv3x3_dgrad_weight': [_P, _P, _I, _I, _P],
     # step plans (csrc/plan.hip): record once, replay with one call
     't3d_plan_create': [ctypes.POINTER(_P)],
     't3d_plan_destroy': [_P],

@@ -33,21 +33,11 @@ BN_EPS, BN_MOM = 1e-5, 0.1      # PyTorch defaults the reference relies on (SURV
 NREP = 16                       # reduction replicas (include/t3d.h: t3d_set_reduction_replicas)
 FUSED_EVAL_MIN_B = int(os.environ.get('T3D_FUSED_EVAL_MIN_B', '96'))
 DW_SLOTS = int(os.environ.get('T3D_DW_SLOTS', '512'))   # depthwise weight-gradient slots per layer (>= the workgroups of a t3d_dwconv_bwd launch)
-PW_FRAG = os.environ.get('T3D_PW_FRAG', '1') != '0'      # fragment-order weights for the 16-bit pointwise kernels (A/B switch)
 WORKSPACE_BYTES = 64 << 20      # partial weight-gradient tiles (include/t3d.h: t3d_set_workspace)
 MAIN_WORKSPACE_BYTES = 16 << 20
 # y-free expand-layer backward (csrc/pwconv_yfree.hip): minimum M*N elements of the expanded tensor; 0 disables
 YFREE_MIN_ELEMS = int(os.environ.get('T3D_YFREE_MIN', 8 << 20))
 YFREE_MAX_K = int(os.environ.get('T3D_YFREE_MAX_K', 112))     # widest narrow side the y-free backward is used for (the K x K Gram terms); round 6: 96 -> 112 takes MobileNetV3-large's two 112 -> 672 expansions at 14x14 (7.59-7.65 -> 7.43 ms per step; 160, the 7x7 stage: 7.53)
-YFREE_FUSED = os.environ.get('T3D_YFREE_FUSED', '1') != '0'     # one-pass expand-layer backward (t3d_pwconv_bwd_yfree)
-YFREE_PREP_FUSED = os.environ.get('T3D_YFREE_PREP_FUSED', '1') != '0'   # ... with its weight rows built in its own prologue (A/B switch)
-EXPDW_EVAL = os.environ.get('T3D_EXPDW_EVAL', '1') != '0'      # fused expand + depthwise forward in 16-bit inference (A/B switch)
-# round 6: the same fused forward in TRAINING, the expansion's BatchNorm statistics taken from the Gram matrix of the narrow block
-# input (csrc/gram.hip).  OPT-IN (T3D_GRAM_FWD_MIN_HW = smallest input plane, in pixels per image, it is used at; 12544 = the
-# 112x112 block, the only stage where the fused launch with the expansion stored beats the two launches alone: DESIGN.md finding
-# 40): measured in the step it is 0.03-0.04 ms SLOWER than the two launches (finding 55), so the default is off.
-GRAM_FWD_MIN_HW = int(os.environ.get('T3D_GRAM_FWD_MIN_HW', 0))
-SE_FOLD = os.environ.get('T3D_SE_FOLD', '1') != '0'   # gated blocks: the BatchNorm-backward finalizes ride on their first reader (round 6; 0: standalone launches)
 HOOK_MIN = 1 << 20              # gradient-exchange granularity (elements): parallel.GradSync's bucket size
 HOOK_ON_SIDE = True              # (round 3: the gradient exchange is issued from the second stream; the other order stalled the main one)
 
@@ -375,7 +365,7 @@ class Net:
                     out = self.w[k].data_ptr()
                 self.wt[k] = self._buf('wt:' + k, (kk, n))
                 fr = frt = 0
-                if self.dt in (N.BF16, N.F16) and PW_FRAG:
+                if self.dt in (N.BF16, N.F16):
                     if lib.t3d_pwconv_wants_frag(kk, n):
                         f = self._buf('wf:' + k, (lib.t3d_pwconv_frag_bytes(n, kk) // 2,), zero=True)
                         self._frag[self.w[k].data_ptr()], fr = f, f.data_ptr()
@@ -452,7 +442,7 @@ class Net:
     # backward half costs nothing either (7.64 ms both ways, 18 launches fewer), so both are on)
     _LAZY_DW = '1'
     DERIVING = frozenset(('t3d_pwconv_fwd', 't3d_pwconv_fwd_mat', 't3d_bn_apply', 't3d_pool_fwd', 't3d_pwconv_dgrad', 't3d_pwconv_yfree_prep',
-                          't3d_pwconv_yfree_prep2', 't3d_conv3x3_dgrad', 't3d_pwconv_bwd_yfree_w', 't3d_se_bwd_affine')
+                          't3d_pwconv_bwd_yfree_w', 't3d_se_bwd_affine')
                          + (('t3d_dwconv_fwd',) if _LAZY_DW in ('1', 'fwd') else ())
                          + (('t3d_dwconv_bwd',) if _LAZY_DW in ('1', 'bwd') else ()))
 
@@ -790,23 +780,12 @@ class Net:
         """Inference mode, bf16 / fp16 storage: may expand + depthwise of this block run as ONE launch (csrc/expdw_fwd.hip)?  In
         training mode the expansion's BatchNorm needs its batch statistics first, which costs a statistics-only pass of the 1x1
         conv (DESIGN.md finding 40: no gain with the raw expansion still stored for the backward)."""
-        if self.training or not EXPDW_EVAL or self.dt not in (N.BF16, N.F16) or x.pro is not None or x.zbuf is not None:
+        if self.training or self.dt not in (N.BF16, N.F16) or x.pro is not None or x.zbuf is not None:
             return False
         if not (blk.expand and not blk.se and blk.k == 3 and isinstance(blk.act, str) and blk.act in ('relu', 'relu6')):
             return False
         # the kernel's own shape tests (channel counts, and an input row no wider than its fragment registers / LDS rows hold:
         # W <= 213 -- a 448 ... 512-pixel crop reaches MobileNetV2's second block wider than that and takes the two launches)
-        return bool(N.lib().t3d_expdw_supported(self.dt, N.ACT[blk.act], x.B, x.H, x.W, blk.cin, blk.cexp, blk.s))
-
-    def _gram_fwd_ok(self, blk, x):
-        """Training mode, bf16: may expand + depthwise of this block run as ONE launch, its BatchNorm statistics coming from the
-        Gram matrix of the block input (one pass over the NARROW tensor, the one that materialises it anyway)?"""
-        if not self.training or not GRAM_FWD_MIN_HW or self.dt != N.BF16 or x.H * x.W < GRAM_FWD_MIN_HW:
-            return False
-        if not (blk.expand and not blk.se and blk.k == 3 and blk.cin in (8, 16) and isinstance(blk.act, str) and blk.act in ('relu', 'relu6')):
-            return False
-        if x.pro is not None and (x.zbuf is None or x.pro.se is not None):
-            return False           # (a deferred activation that is not a pending block output: the two launches)
         return bool(N.lib().t3d_expdw_supported(self.dt, N.ACT[blk.act], x.B, x.H, x.W, blk.cin, blk.cexp, blk.s))
 
     def _block_fwd(self, i, blk, x, sv):
@@ -847,38 +826,7 @@ class Net:
             x = self._finish(x, f'z:in{i}')
         rec = dict(x=x)
         src = x
-        fused_dw = False
-        if blk.expand and self._gram_fwd_ok(blk, x):
-            # training, the 112x112 expansion: [materialise the block input + its Gram matrix] -> BatchNorm coefficients of the
-            # expansion from the K x K sums -> expand + BatchNorm + activation + depthwise in ONE launch, the raw expansion
-            # stored for the backward (csrc/gram.hip, csrc/expdw_fwd.hip; DESIGN.md finding 55)
-            bn1, bn2 = self.bns[p + '.1'], self.bns[p + '.4']
-            M, K, C = B * H * W, blk.cin, blk.cexp
-            gram = self._buf(f'gram:{i}', (16, K * (K + 1) // 2 + K), torch.float64, zgroup='fwd')      # 16 reduction replicas
-            if x.zbuf is not None:
-                self._settle_f(x.bn)
-                N.call('t3d_bn_apply_gram', dt, N.ptr(x.t), x.pro, N.ptr(x.zres), N.ptr(x.zbuf), N.ptr(gram), M, K, st,
-                       nbytes=2 * M * K * self.esz)
-                x.t, x.pro, x.zres, x.zbuf = x.zbuf, None, None, None
-            else:
-                N.call('t3d_bn_apply_gram', dt, N.ptr(x.t), None, None, None, N.ptr(gram), M, K, st, nbytes=M * K * self.esz)
-            N.call('t3d_gram_bn_finalize', N.ptr(gram), N.ptr(self.w[p + '.0.weight']), C, K, float(M), N.ptr(bn1.gamma),
-                   N.ptr(bn1.beta), N.ptr(bn1.rm), N.ptr(bn1.rv), N.ptr(bn1.nbt), BN_MOM, BN_EPS, N.ptr(bn1.scale), N.ptr(bn1.shift),
-                   N.ptr(bn1.mean), N.ptr(bn1.invstd), st)
-            bn1.count, bn1.pend[0] = float(M), False
-            Ho, Wo = (H + 2 - 3) // blk.s + 1, (W + 2 - 3) // blk.s + 1
-            M2 = B * Ho * Wo
-            y1 = self._buf(f'y1:{i}', (M, C))
-            y2 = self._buf(f'y2:{i}', (M2, C))
-            N.call('t3d_expdw_fwd', dt, N.ptr(x.t), N.ptr(self.w[p + '.0.weight']), N.ptr(bn1.scale), N.ptr(bn1.shift),
-                   N.ACT[blk.act], N.ptr(self.p[p + '.3.weight']), N.ptr(y1), N.ptr(y2), self._st(bn2), B, H, W, K, C, blk.s, st,
-                   nbytes=(M * K + 2 * M * C + M2 * C) * self.esz)      # (the two launches' algorithmic bytes, SURVEY 8d: fused > 1 is legitimate)
-            pro1 = self._pro(bn1, blk.act)
-            src = _Src(y1, pro1, B, H, W, C, raw=y1, bn=bn1, gpro=pro1)
-            rec['s1'] = src
-            dwn, bnn, pwn, bn3n = p + '.3.weight', p + '.4', p + '.7.weight', p + '.8'
-            fused_dw = True
-        elif blk.expand:                                                  # mobilenetv3.py:146-150
+        if blk.expand:                                                    # mobilenetv3.py:146-150
             bn1 = self.bns[p + '.1']
             M = B * H * W
             y1 = self._buf(f'y1:{i}', (M, blk.cexp))
@@ -901,10 +849,9 @@ class Net:
         # add integers, so the sums, the gate and everything behind it no longer depend on their arrival order
         gap = self._buf(f'gap:{i}', (B, blk.cexp), torch.int64, zgroup='fwd') if (blk.se and not se_after) else None
         self._pool_exact(gap is not None)
-        if not fused_dw:
-            self._c('t3d_dwconv_fwd', dt, N.ptr(src.t), src.pro, N.ptr(self.p[dwn]), N.ptr(y2), self._st(bn2), N.ptr(gap),
-                    B, H, W, blk.cexp, blk.k, blk.s, st, nbytes=(B * H * W + M2) * blk.cexp * self.esz,
-                    fwd=src.bn if src.pro is not None else None)
+        self._c('t3d_dwconv_fwd', dt, N.ptr(src.t), src.pro, N.ptr(self.p[dwn]), N.ptr(y2), self._st(bn2), N.ptr(gap),
+                B, H, W, blk.cexp, blk.k, blk.s, st, nbytes=(B * H * W + M2) * blk.cexp * self.esz,
+                fwd=src.bn if src.pro is not None else None)
         pro2 = self._bn_fwd(bn2, M2, blk.act)
         if blk.se:
             self._settle_f(bn2)          # the squeeze-excite kernels read bn2's affine first
@@ -969,11 +916,10 @@ class Net:
         ro = kw.pop('ro', None)
         # ro: BatchNorm whose backward coefficients this launch reads while their finalize is still pending -- the kernel
         # derives them for itself WITHOUT publishing (the data-gradient launch of the main stream, issued next, does)
-        # (only where the bf16 transposed kernel will take the request: on the fp32-storage / T3D_WGRAD_TILED paths the entry
-        # point would serve it with a PUBLISHING finalize launch on the side stream while the data gradient of the main
-        # stream publishes the same values -- there the standalone finalize runs once, on the main stream, ahead of both)
-        req = (ro is not None and ro.pend[1] and self._lazy and entry in ('t3d_pwconv_wgrad', 't3d_conv3x3_wgrad') and self.dt == N.BF16
-               and not os.environ.get('T3D_WGRAD_TILED'))
+        # (only where the bf16 transposed kernel will take the request: on the fp32-storage path the entry point would serve
+        # it with a PUBLISHING finalize launch on the side stream while the data gradient of the main stream publishes the
+        # same values -- there the standalone finalize runs once, on the main stream, ahead of both)
+        req = ro is not None and ro.pend[1] and self._lazy and entry == 't3d_pwconv_wgrad' and self.dt == N.BF16
         if ro is not None and ro.pend[1] and not req:
             self._settle_b(ro)
         if req:
@@ -1232,23 +1178,15 @@ class Net:
         # ONE pass over the wide gradient for both products (csrc/pwconv_wgrad_tr.hip, DGF): the data gradient and the partial
         # tiles of the weight-gradient products come out of the same staged rows on the main stream; the second stream only
         # reduces and combines.  (The pair below reads d1 twice, from two streams at the same time.)
-        need = N.lib().t3d_pwconv_bwd_yfree_scratch(M, K, Nn) if (YFREE_FUSED and not (with_stats and x.gpro is not None)) else 0
+        need = N.lib().t3d_pwconv_bwd_yfree_scratch(M, K, Nn) if not (with_stats and x.gpro is not None) else 0
         if need > 0:
             scratch = self._buf(f'yfscr:{i}', (need,), torch.uint8)
             dx = self._buf(f'dzin:{i}', (M, K))
-            if YFREE_PREP_FUSED:
-                # the data gradient's weight rows are built in the launch's own prologue (and the BatchNorm-backward finalize
-                # derived there): no t3d_pwconv_yfree_prep2 launch on the critical stream (round 5: -13 us x 6 per step)
-                self._c('t3d_pwconv_bwd_yfree_w', N.ptr(d1), N.ptr(x.t), N.ptr(self.wt[wname]), bb1, N.ptr(x.raw) if with_stats else None,
-                        None, N.ptr(res) if res is not None else None, N.ptr(dx), self._bst(x.bn) if with_stats else None,
-                        N.ptr(scratch), need, M, HW, K, Nn, st, nbytes=M * (K + Nn) * self.esz, bwd=bn1)
-            else:
-                key = (f'wd:{i}', ((K + 15) // 16 * 16, (Nn + K + 8 + 63) // 64 * 64), self.dtype)
-                wd = self._bufs.get(key) if key in self._bufs else self._buf(key[0], key[1], zero=True)   # cleared ONCE: prep2 writes the non-zero entries
-                self._c('t3d_pwconv_yfree_prep2', N.ptr(self.wt[wname]), bb1, N.ptr(wcat), N.ptr(cvec), N.ptr(wd), K, Nn, st, bwd=bn1)
-                N.call('t3d_pwconv_bwd_yfree', N.ptr(d1), N.ptr(x.t), N.ptr(wd), N.ptr(x.raw) if with_stats else None, None,
-                       N.ptr(res) if res is not None else None, N.ptr(dx), self._bst(x.bn) if with_stats else None, N.ptr(scratch), need,
-                       M, HW, K, Nn, st, nbytes=M * (K + Nn) * self.esz)
+            # the data gradient's weight rows are built in the launch's own prologue (and the BatchNorm-backward finalize
+            # derived there): no t3d_pwconv_yfree_prep2 launch on the critical stream (round 5: -13 us x 6 per step)
+            self._c('t3d_pwconv_bwd_yfree_w', N.ptr(d1), N.ptr(x.t), N.ptr(self.wt[wname]), bb1, N.ptr(x.raw) if with_stats else None,
+                    None, N.ptr(res) if res is not None else None, N.ptr(dx), self._bst(x.bn) if with_stats else None,
+                    N.ptr(scratch), need, M, HW, K, Nn, st, nbytes=M * (K + Nn) * self.esz, bwd=bn1)
             self._wgrad(N.ptr(scratch), bb1, N.ptr(self.w[wname]), N.ptr(self.g[wname]), M, K, Nn, entry='t3d_pwconv_wgrad_yfree_finish')
             if x.finished_act:
                 dx = self._act_bwd(dx, x, f'dzin:{i}:a')
@@ -1281,8 +1219,6 @@ class Net:
         M2, HW2 = s2.B * s2.H * s2.W, s2.H * s2.W
         bb3 = self._bn_bwd(rec['bn3'])
         se = rec.get('se')
-        if se is not None and not SE_FOLD:
-            self._settle_b(rec['bn3'])
 
         def proj_wgrad():
             self._wgrad(dt, N.ptr(dz), N.ptr(rec['y3']), bb3, N.ptr(s2.t), s2.pro, N.ptr(self.g[pwn]),
@@ -1340,8 +1276,6 @@ class Net:
                    B, C, R, se['HW'], st)
             self._se_wgrad(se, sen, dq, dp, B, C, R)
             self._bn_bwd(bn2)
-            if not SE_FOLD:
-                self._settle_b(bn2)
             aps = self._buf(f'se_aps:{i}', (B, C), torch.float32)
             gps = self._buf(f'se_gps:{i}', (B, C), torch.float32)
             self._c('t3d_se_bwd_affine', N.ptr(se['s']), N.ptr(g), N.ptr(bn2.alpha), N.ptr(bn2.gammac), N.ptr(aps),

@@ -259,23 +259,6 @@ int t3d_augment_crops_u8(const unsigned char* src, long long src_bytes, const vo
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
                  void* stream);
 
-/* Round 6: the BatchNorm statistics of an expansion conv from the Gram matrix of its narrow input (csrc/gram.hip).  For
- * y1 = W1 z (models/mobilenetv3.py:146-148: nn.Conv2d(inp, hidden_dim, 1) + nn.BatchNorm2d(hidden_dim)), sum(y1) = W1 (1^T z)
- * and sum(y1^2)_c = w_c^T (z^T z) w_c: one pass over the NARROW tensor replaces the statistics the 1x1 conv's epilogue takes
- * over the 6x wider one -- which is what lets the fused expand + depthwise forward (t3d_expdw_fwd) run in TRAINING mode.
- *   t3d_bn_apply_gram: t3d_bn_apply (z may be NULL: y is the finished tensor already, pro and residual NULL) that also adds
- *     [upper triangle of z^T z, row-major (i, j >= i) | 1^T z] into gram [16][K(K+1)/2 + K] fp64 -- 16 reduction replicas, a
- *     workgroup adds into one of them (caller zeroes all; order-independent adds); bf16, K in {8, 16}; the sums are those of the
- *     STORED (rounded) z.
- *   t3d_gram_bn_finalize: t3d_bn_finalize's outputs (scale, shift, mean, invstd, running statistics, num_batches_tracked) for
- *     the C channels of W1 z from those sums (the 16 replicas added first); w [C,K] in the conv's storage dtype (bf16: the matrix
- *     the MFMA multiplies). */
-int t3d_bn_apply_gram(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, double* gram, int M,
-                      int K, void* stream);
-int t3d_gram_bn_finalize(const double* gram, const void* w, int C, int K, double count, const float* gamma, const float* beta,
-                         float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
-                         float* scale, float* shift, float* mean_out, float* invstd_out, void* stream);
-
 /* Backward of t3d_bn_apply's activation:  dzp = dz * act'(scale*y + shift);
  * stats [2*C] fp64 += sum(dzp), sum(dzp*y) (caller zeroes). */
 int t3d_bn_act_bwd(int dtype, const void* dz, const void* y, const t3d_prologue* pro, void* dzp, double* stats,
@@ -591,28 +574,6 @@ int t3d_dropout_mask(float* mask, long long n, unsigned long long seed, unsigned
 /* Zero fill of several device buffers in one launch: desc = n rows of int64 {ptr, bytes}, bytes % 16 == 0, DEVICE array
  * (the per-step clears of the gradient buffer, the BatchNorm sum replicas and the depthwise weight-gradient replicas). */
 int t3d_zero_batched(const long long* desc, int n, void* stream);
-
-/* Dense 3x3 convolution (pad 1, stride 1 or 2) as an implicit GEMM, bf16 storage (round 5; csrc/conv3x3.hip): the three GEMMs of
- * ResNet-50's conv2 layers gather their operand rows from the activation tensor themselves -- no patch matrix in HBM.  Replaces
- * nn.Conv2d(C, N, 3, stride, 1, bias=False) and its autograd in a torchvision Bottleneck, the backbone BASELINE config 4 builds
- * through torchdet3d/builders/model_builder.py:73-151 (t3d_im2col / t3d_col2im_bwd + the 1x1 kernels remain for fp32 storage
- * and the 7x7 stem).  C a power of two >= 32 (the weight gradient: N >= 64 as well), N % 8 == 0.
- *   _fwd    dtype = T3D_BF16 | T3D_W_FRAG; x [B,H,W,C] raw + `pro` (BatchNorm affine + activation of its producer, may be NULL);
- *           w_frag = t3d_pwconv_pack_frag of the [N][9C] patch-column-order weights (t3d_pack_conv_weight);
- *           y [B,Ho,Wo,N] raw, stats [2N] fp64 replicas or NULL as t3d_pwconv_fwd;
- *   _dgrad  dx [B,H,W,C] = gradient at the producer's BatchNorm output: sum over (tap, n) of the BatchNorm-backward affine of
- *           (dz, y) [B,Ho,Wo,N] times wd, times act'(x_raw through pro_in), stats += sum(dx), sum(dx * x_raw) as t3d_pwconv_dgrad;
- *           wd_frag = t3d_pwconv_pack_frag of the [C][9N] matrix t3d_pack_conv3x3_dgrad_weight writes (wd[c][t*N+n] = w[n][c][t]);
- *   _wgrad  dw_packed [N][9C] fp32 = (BatchNorm-backward affine of (dz, y))^T * gathered act(x) (written, not added to), patch-column order
- *           (t3d_unpack_conv_grad -> [N][C][3][3]); dtype T3D_BF16; the caller's workspace as t3d_pwconv_wgrad. */
-int t3d_conv3x3_fwd(int dtype, const void* x, const t3d_prologue* pro, const void* w_frag, void* y, double* stats, int B, int H,
-                    int W, int C, int N, int stride, void* stream);
-int t3d_conv3x3_dgrad(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const void* wd_frag, const void* x_raw,
-                      const t3d_prologue* pro_in, void* dx, double* stats, int B, int H, int W, int C, int N, int stride,
-                      void* stream);
-int t3d_conv3x3_wgrad(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const void* x, const t3d_prologue* pro,
-                      float* dw_packed, int B, int H, int W, int C, int N, int stride, void* stream);
-int t3d_pack_conv3x3_dgrad_weight(const float* w, void* out, int N, int C, void* stream);
 
 /* Fused expand 1x1 conv + BatchNorm + activation + depthwise 3x3 conv forward of an inverted-residual block (round 5;
  * csrc/expdw_fwd.hip): y2 = dwconv3x3(act(scale1 * round(W1 z) + shift1)), dtype T3D_BF16 or T3D_F16 (inference), K <= 32 (the 112x112 .. 28x28 blocks of

@@ -294,17 +294,15 @@ def test_pwconv_fwd_mat_f32_inference_one_launch(M, K, N, res, train):
         np.testing.assert_allclose(st[1].cpu().numpy(), (y[:M].double() ** 2).sum(0).cpu().numpy(), rtol=1e-5, atol=1e-4)
 
 
-# bf16 materialising forward of the small planes' expansions with FRAGMENT-ORDER weights: csrc/pwconv_wide.hip (operand staged once,
-# all output channels per workgroup) where the shape is one of its own, else the streaming kernel on the same layout; against
+# bf16 materialising forward of the small planes' expansions with FRAGMENT-ORDER weights: the streaming kernel on that layout; against
 # t3d_bn_apply (z, bit for bit) and an fp64 product of the stored z; ragged pixel counts, contractions that are not a multiple of 32
 # (80, 112, 200 outputs that end inside a 32-channel pair), statistics into replicas with a stride wider than the row
 @pytest.mark.parametrize('M,K,N', [(1568, 160, 960), (1000, 64, 384), (777, 96, 576), (640, 320, 1280), (900, 80, 200), (1031, 112, 672),
                                    (513, 40, 120), (300, 24, 144), (2048, 16, 96)])
 @pytest.mark.parametrize('res', [False, True])
 @pytest.mark.parametrize('act', ['none', 'relu6', 'hswish'])
-def test_pwconv_fwd_mat_bf16_fragment_order_weights(M, K, N, res, act, monkeypatch):
+def test_pwconv_fwd_mat_bf16_fragment_order_weights(M, K, N, res, act):
     from torchdet3d import _native as Nt
-    monkeypatch.setenv('T3D_PW_WIDE', '1')      # (opt-in kernel, csrc/pwconv_wide.hip; read per call)
     g = torch.Generator().manual_seed(M + K + N + res)
     bf = torch.bfloat16
     y3 = torch.randn(M, K, generator=g).cuda().to(bf)

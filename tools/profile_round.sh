@@ -18,7 +18,6 @@ python3 bench.py --full --steps 20 --warmup 5 --model resnet50 --batch 64 --no-c
 python3 bench.py --full --steps 30 --warmup 8 --engine --no-cpu-baseline > $o/bench_bf16_engine_loop.json 2> /dev/null
 T3D_STEP_PLAN=0 python3 bench.py --full --steps 30 --warmup 8 --no-cpu-baseline > $o/bench_bf16_direct_step.json 2> /dev/null
 T3D_PLAN_HANDOFF=0 python3 bench.py --full --steps 30 --warmup 8 --no-cpu-baseline > $o/bench_bf16_event_forks.json 2> /dev/null
-T3D_IMPLICIT3=1 python3 bench.py --full --steps 20 --warmup 5 --model resnet50 --batch 64 --no-cpu-baseline > $o/bench_resnet50_implicit3x3.json 2> /dev/null
 python3 tools/time_expdw.py > $o/expdw_fused_forward_timings.txt 2>&1
 python3 tools/time_pw_f32.py > $o/pw_f32_reg_vs_tiled.txt 2>&1
 bash tools/time_kernels.sh > $o/isolated_kernel_timings.txt 2>&1

@@ -1,6 +1,6 @@
 """Isolated timing of the fp32-storage inference 1x1 conv on MobileNetV2's layer shapes at batch 256: the register-operand kernel
-(csrc/pwconv_f32_reg.hip) against round 1's LDS-tiled one (T3D_F32_TILED=1); --sweep: every task shape R x NT x V.
-usage: python tools/time_pw_f32.py [--sweep]"""
+(csrc/pwconv_f32_reg.hip) against round 1's LDS-tiled one (T3D_F32_TILED=1).
+usage: python tools/time_pw_f32.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, '3d-object-detection.pytorch_amd')]
@@ -37,20 +37,7 @@ for hw, K, Nn, cnt in [(112, 32, 16, 1), (112, 16, 96, 1), (56, 96, 24, 1), (56,
     os.environ['T3D_F32_TILED'] = '1'
     t1 = timeit(f)
     os.environ.pop('T3D_F32_TILED', None)
-    sweep = ''
-    if '--sweep' in sys.argv:
-        res = []
-        for V in (1,):
-            for R in (1, 2, 4):
-                for NT in (2, 3, 4, 5, 6):
-                    if R == 1:
-                        continue
-                    os.environ['T3D_F32_SHAPE'] = f'{R}{NT}'
-                    res.append((timeit(f, 10), R, NT, V))
-        os.environ.pop('T3D_F32_SHAPE', None)
-        res.sort()
-        sweep = '  best ' + ' '.join(f'{R}x{NT}x{V}:{t:.0f}' for t, R, NT, V in res[:5])
     gb = M * (K + Nn) * 4 / 1e3
     tot[0] += cnt * t0; tot[1] += cnt * t1
-    print(f'{hw:4d}^2 {K:4d}->{Nn:4d} x{cnt}: reg {t0:6.1f} us {gb / t0:5.0f} GB/s {2e-6 * M * K * Nn / t0:5.1f} TF/s  tiled {t1:6.1f} us' + sweep)
+    print(f'{hw:4d}^2 {K:4d}->{Nn:4d} x{cnt}: reg {t0:6.1f} us {gb / t0:5.0f} GB/s {2e-6 * M * K * Nn / t0:5.1f} TF/s  tiled {t1:6.1f} us')
 print(f'per forward: reg {tot[0] / 1e3:.2f} ms, tiled {tot[1] / 1e3:.2f} ms')
