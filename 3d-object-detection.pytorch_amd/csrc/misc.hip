@@ -164,6 +164,108 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   if (watch && __any(bad) && (threadIdx.x & 63) == 0) atomicMin(reinterpret_cast<unsigned long long*>(watch), (unsigned long long)step);
 }
 
+// SGD / RMSprop / Adadelta over one flat fp32 buffer: torch.optim's single-tensor arithmetic with coupled weight decay
+// (g' = g + wd*p, skipped when wd == 0 as torch skips it), operation by operation in torch's order (the build has
+// -ffp-contract=off, so every product and sum below is rounded on its own like the framework's separate passes).  Same
+// shape as adamw_kernel: 16 B per lane per array, grid-stride, the gradient read as gscale * g, the divergence watch at the end.
+__device__ __forceinline__ void grad_watch_report(bool bad, long long* watch, long long step) {
+  if (watch && __any(bad) && (threadIdx.x & 63) == 0) atomicMin(reinterpret_cast<unsigned long long*>(watch), (unsigned long long)step);
+}
+
+// MODE 0: no momentum (buf is not touched and may be null), 1: momentum, 2: Nesterov momentum.  Dampening is 0, so a zeroed
+// buffer gives torch's first step (buf = g') exactly.
+//   buf = momentum*buf + g';  d = g' + momentum*buf (Nesterov) | buf | g';  p -= lr*d
+template <int MODE>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  long long n4, float lr, float momentum, float wd, float gscale,
+                                                  long long* watch, long long step) {
+  bool bad = false;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg4 = reinterpret_cast<const float4*>(g)[i];
+    float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MODE != 0) bb = reinterpret_cast<float4*>(buf)[i];
+    float* pe = reinterpret_cast<float*>(&pp);
+    const float* ge = reinterpret_cast<const float*>(&gg4);
+    float* be = reinterpret_cast<float*>(&bb);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gj = ge[j] * gscale;
+      bad |= !(fabsf(gj) <= 3.4028235e38f);                         // inf or NaN
+      if (wd != 0.f) gj = gj + wd * pe[j];
+      float d = gj;
+      if constexpr (MODE != 0) {
+        be[j] = be[j] * momentum + gj;
+        d = MODE == 2 ? gj + momentum * be[j] : be[j];
+      }
+      pe[j] = pe[j] - lr * d;
+    }
+    reinterpret_cast<float4*>(p)[i] = pp;
+    if constexpr (MODE != 0) reinterpret_cast<float4*>(buf)[i] = bb;
+  }
+  grad_watch_report(bad, watch, step);
+}
+
+//   sq = alpha*sq + (1-alpha)*g'^2;  p -= lr * (g' / (sqrt(sq) + eps))          (not centered, no momentum)
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
+                                                      long long n4, float lr, float alpha, float oma, float eps, float wd,
+                                                      float gscale, long long* watch, long long step) {
+  bool bad = false;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg4 = reinterpret_cast<const float4*>(g)[i];
+    float4 ss = reinterpret_cast<float4*>(sq)[i];
+    float* pe = reinterpret_cast<float*>(&pp);
+    const float* ge = reinterpret_cast<const float*>(&gg4);
+    float* se = reinterpret_cast<float*>(&ss);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gj = ge[j] * gscale;
+      bad |= !(fabsf(gj) <= 3.4028235e38f);
+      if (wd != 0.f) gj = gj + wd * pe[j];
+      const float sj = se[j] * alpha + oma * (gj * gj);              // 1 - alpha taken in fp64 on the host
+      const float avg = sqrtf(sj) + eps;
+      pe[j] = pe[j] - lr * (gj / avg);
+      se[j] = sj;
+    }
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(sq)[i] = ss;
+  }
+  grad_watch_report(bad, watch, step);
+}
+
+//   sq = rho*sq + (1-rho)*g'^2;  delta = sqrt(acc + eps) / sqrt(sq + eps) * g';  acc = rho*acc + (1-rho)*delta^2;  p -= lr*delta
+__global__ __launch_bounds__(256) void adadelta_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
+                                                       float* __restrict__ acc, long long n4, float lr, float rho, float omr,
+                                                       float eps, float wd, float gscale, long long* watch, long long step) {
+  bool bad = false;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg4 = reinterpret_cast<const float4*>(g)[i];
+    float4 ss = reinterpret_cast<float4*>(sq)[i];
+    float4 aa = reinterpret_cast<float4*>(acc)[i];
+    float* pe = reinterpret_cast<float*>(&pp);
+    const float* ge = reinterpret_cast<const float*>(&gg4);
+    float* se = reinterpret_cast<float*>(&ss);
+    float* ae = reinterpret_cast<float*>(&aa);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gj = ge[j] * gscale;
+      bad |= !(fabsf(gj) <= 3.4028235e38f);
+      if (wd != 0.f) gj = gj + wd * pe[j];
+      const float sj = se[j] * rho + omr * (gj * gj);                // 1 - rho taken in fp64 on the host
+      const float delta = sqrtf(ae[j] + eps) / sqrtf(sj + eps) * gj;
+      ae[j] = ae[j] * rho + omr * (delta * delta);
+      pe[j] = pe[j] - lr * delta;
+      se[j] = sj;
+    }
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(sq)[i] = ss;
+    reinterpret_cast<float4*>(acc)[i] = aa;
+  }
+  grad_watch_report(bad, watch, step);
+}
+
 // dst [rows][cd] <- src [rows][cs]: the leading min(cs, cd) columns are copied, further dst columns zeroed
 __global__ void copy_cols_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows, int cs, int cd) {
   const int n = rows * cd;
@@ -280,6 +382,43 @@ extern "C" int t3d_adamw_step(float* p, const float* g, float* m, float* v, long
   T3D_LAUNCH(adamw_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n4,
                      (float)(1.0 - lr * weight_decay), (float)(1.0 - b1d), (float)beta2, (float)(1.0 - b2d),
                      (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)eps, (float)grad_scale, g_grad_watch, step);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+static inline int t3d_stream_grid(long long n4) { return (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048); }
+
+extern "C" int t3d_sgd_step(float* p, const float* g, float* buf, long long n, double lr, double momentum, double weight_decay,
+                            int nesterov, long long step, double grad_scale, void* stream) {
+  if (!p || !g || n <= 0 || (n % 4) || step <= 0) return T3D_ERR_ARG;
+  if (momentum != 0.0 ? !buf : nesterov != 0) return T3D_ERR_ARG;     // (Nesterov needs a momentum, as torch.optim.SGD insists)
+  const long long n4 = n / 4;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float lrf = (float)lr, mf = (float)momentum, wdf = (float)weight_decay, gs = (float)grad_scale;
+  if (momentum == 0.0) T3D_LAUNCH(sgd_kernel<0>, dim3(t3d_stream_grid(n4)), dim3(256), 0, st, p, g, buf, n4, lrf, mf, wdf, gs, g_grad_watch, step);
+  else if (!nesterov) T3D_LAUNCH(sgd_kernel<1>, dim3(t3d_stream_grid(n4)), dim3(256), 0, st, p, g, buf, n4, lrf, mf, wdf, gs, g_grad_watch, step);
+  else T3D_LAUNCH(sgd_kernel<2>, dim3(t3d_stream_grid(n4)), dim3(256), 0, st, p, g, buf, n4, lrf, mf, wdf, gs, g_grad_watch, step);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+extern "C" int t3d_rmsprop_step(float* p, const float* g, float* sq, long long n, double lr, double alpha, double eps,
+                                double weight_decay, long long step, double grad_scale, void* stream) {
+  if (!p || !g || !sq || n <= 0 || (n % 4) || step <= 0) return T3D_ERR_ARG;
+  const long long n4 = n / 4;
+  // 1 - alpha in fp64 like the Python float PyTorch passes as addcmul's `value`, only then rounded (see t3d_adamw_step)
+  T3D_LAUNCH(rmsprop_kernel, dim3(t3d_stream_grid(n4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, sq, n4,
+             (float)lr, (float)alpha, (float)(1.0 - alpha), (float)eps, (float)weight_decay, (float)grad_scale, g_grad_watch, step);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+extern "C" int t3d_adadelta_step(float* p, const float* g, float* sq, float* acc, long long n, double lr, double rho, double eps,
+                                 double weight_decay, long long step, double grad_scale, void* stream) {
+  if (!p || !g || !sq || !acc || n <= 0 || (n % 4) || step <= 0) return T3D_ERR_ARG;
+  const long long n4 = n / 4;
+  T3D_LAUNCH(adadelta_kernel, dim3(t3d_stream_grid(n4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, sq, acc, n4,
+             (float)lr, (float)rho, (float)(1.0 - rho), (float)eps, (float)weight_decay, (float)grad_scale, g_grad_watch, step);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }

@@ -115,6 +115,9 @@ SIGNATURES = {
     't3d_iou3d': [_P, _P, _I, _I, _P, _P, _P, _P, _P],
     't3d_box_iou3d': [_P, _I, _P, _P, _P],
     't3d_adamw_step': [_P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _L, _D, _P],
+    't3d_sgd_step': [_P, _P, _P, _L, _D, _D, _D, _I, _L, _D, _P],
+    't3d_rmsprop_step': [_P, _P, _P, _L, _D, _D, _D, _D, _L, _D, _P],
+    't3d_adadelta_step': [_P, _P, _P, _P, _L, _D, _D, _D, _D, _L, _D, _P],
     't3d_set_grad_watch': [_P],
     't3d_zero_batched': [_P, _I, _P],
     't3d_copy_cols': [_P, _P, _I, _I, _I, _P],

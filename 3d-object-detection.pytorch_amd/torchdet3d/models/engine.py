@@ -642,6 +642,7 @@ class Net:
         finally:
             self._want_taps = None
             N.call('t3d_set_reduction_replicas', 1, 0)
+            self._pool_exact(False)          # (process-wide like the replicas: the last squeeze-excite block left it on)
             self._cur_nrep = None
         return {k: (s.t, s.B, s.H, s.W, s.C) for k, s in sv['taps'].items()}
 
@@ -655,6 +656,7 @@ class Net:
             sv = self._features(imgs, False)
         finally:
             N.call('t3d_set_reduction_replicas', 1, 0)
+            self._pool_exact(False)          # (see forward_taps)
             self._cur_nrep = None
         cur, a = sv['last_in'], self.arch
         M = sv['B'] * cur.H * cur.W

@@ -5,7 +5,8 @@ Three forms of the same step, bit-identical to each other (tests/test_gpu_step_p
 
   eager    `Trainer.train_step`'s reference-shaped sequence through autograd (`model(...)`, `LossManager.parse_losses`,
            `loss.backward()`, `optimizer.step()`): what runs for anything this module does not cover (user criterions, ALWA,
-           a framework optimizer, host-side inputs);
+           a framework optimizer built by hand -- `build_optimizer` returns a kernel optimizer for every name --, host-side
+           inputs);
   direct   the same entry points issued from Python in step order WITHOUT the autograd glue: the loss launch hands its
            gradients straight to `engine.backward`, the optimizer kernel reads the engine's gradient buffer -- no framework
            kernel (fill / clone / multiply by the upstream gradient / gradient copy) is left inside the step;
@@ -43,12 +44,12 @@ class StepPlan:
     @staticmethod
     def usable(model, lm, opt):
         from ..builders.model_builder import ModelWrapper
-        from ..builders.optim_builder import FusedAdamW
+        from ..builders.optim_builder import FusedOptimizer
         if not isinstance(model, ModelWrapper) or model.export_mode or model.net.device.type != 'cuda':
             return False
         if lm is None or not getattr(lm, '_fused', False) or lm.use_alwa:
             return False            # (ALWA reads loss values back on the host every C-th iteration: the eager form does that)
-        if not isinstance(opt, FusedAdamW) or len(opt.param_groups) != 1:
+        if not isinstance(opt, FusedOptimizer) or len(opt.param_groups) != 1:      # (any of the four kernel optimizers)
             return False
         ps = opt.param_groups[0]['params']
         return len(ps) == 1 and ps[0] is model.flat
@@ -64,22 +65,11 @@ class StepPlan:
                 and imgs.device == m.net.device)
 
     def _key(self, imgs):
-        net, g = self.model.net, self.opt.param_groups[0]
-        st = self._state()
+        net = self.model.net
+        # (the optimizer's part -- its class, hyper-parameters other than lr, state pointers -- is the optimizer's to name)
         return (id(net), tuple(imgs.shape), imgs.dtype, N.stream(), id(net._side), bytes(self.lm.loss_cfg()),
-                tuple(g['betas']), g['eps'], g['weight_decay'], self.opt.grad_scale, torch.initial_seed(),
-                id(net.grad_hook), net.num_classes,
-                st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr())
-
-    def _state(self):
-        """The optimizer's state of the flat parameter, created as FusedAdamW.step creates it (builders/optim_builder.py)."""
-        p = self.model.flat
-        state = self.opt.state[p]
-        if not state:
-            state['step'] = 0
-            state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        return state
+                self.opt.plan_key(self.model.flat, self.opt.param_groups[0]), torch.initial_seed(),
+                id(net.grad_hook), net.num_classes)
 
     # ------------------------------------------------------------------ the step
     def run(self, imgs, gt_kp, cats, slot):
@@ -154,25 +144,17 @@ class StepPlan:
                 if rec is not None:
                     rec.host_break(('finish',))
                 sync.finish()
-            # optimizer (builders/optim_builder.py: FusedAdamW.step, one parameter)
-            g = opt.param_groups[0]
+            # optimizer: the launch `optimizer.step()` issues (builders/optim_builder.py), reading the engine's gradient buffer,
+            # with lr and the step count named as slots
             p = model.flat
-            state = self._state()
-            state['step'] += 1
-            b1, b2 = g['betas']
-            N.call('t3d_set_grad_watch', N.ptr(opt.watch_word(p.device)))
-            N.call('t3d_adamw_step', N.ptr(p), N.ptr(net.gflat), N.ptr(state['exp_avg']), N.ptr(state['exp_avg_sq']), p.numel(),
-                   float(g['lr']), float(b1), float(b2), float(g['eps']), float(g['weight_decay']), state['step'],
-                   float(opt.grad_scale), st, slots={5: N.SLOT_LR, 10: N.SLOT_STEP})
-            N.call('t3d_set_grad_watch', None)
-            torch.autograd.graph.increment_version(p)
+            opt.launch(p, net.gflat, st, slots=True, group=opt.param_groups[0])
             if p.grad is not net.gflat:
                 p.grad = net.gflat                           # what `loss.backward()` leaves in the eager form
             if rec is not None:
                 if not rb_side:
                     rec.add_readback(N.SLOT_RB_DST, out, 64, N.SLOT_RB_EVENT, st)
                 rec.end_segment()
-                rec.keep += [out, dkp, dlg, kp, logits, state['exp_avg'], state['exp_avg_sq']]
+                rec.keep += [out, dkp, dlg, kp, logits, *opt.state_tensors(p)]
         except BaseException:
             if rec is not None:
                 rec.close()                              # (an exception while recording must not leak the plan)
@@ -192,12 +174,11 @@ class StepPlan:
         model, opt, rec = self.model, self.opt, self.rec
         net = model.net
         g, p = opt.param_groups[0], model.flat
-        state = opt.state[p]
-        state['step'] += 1
+        step = opt.advance(p)
         net._dropout_calls = getattr(net, '_dropout_calls', 0) + 1
         s = self.slots
         s[N.SLOT_IMGS], s[N.SLOT_GT], s[N.SLOT_CATS] = imgs.data_ptr(), gt_kp.data_ptr(), cats.data_ptr()
-        s[N.SLOT_DROPOUT], s[N.SLOT_STEP], s[N.SLOT_LR] = net._dropout_calls, state['step'], N.double_bits(g['lr'])
+        s[N.SLOT_DROPOUT], s[N.SLOT_STEP], s[N.SLOT_LR] = net._dropout_calls, step, N.double_bits(g['lr'])
         s[N.SLOT_RB_DST], s[N.SLOT_RB_EVENT] = slot[0].data_ptr(), slot[1].cuda_event
         lib, plan = N.lib(), rec.plan
         ev = self.timing

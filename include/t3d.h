@@ -546,9 +546,29 @@ int t3d_pack_weights_batched(int dtype, const long long* desc, int n, void* stre
  * caller-owned moment buffers (zeroed before the first step). */
 int t3d_adamw_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, long long step, double grad_scale, void* stream);
+/* The other three names of build_optimizer (torchdet3d/builders/optim_builder.py:3-19), same contract as t3d_adamw_step: ONE
+ * launch over the flat fp32 buffer (n % 4 == 0), g read as grad_scale * g, state buffers caller-owned and zeroed before the
+ * first step, `step` the 1-based step count (what the divergence watch below reports), `lr` and `step` at fixed positions so
+ * that a step plan binds them to slots.  The arithmetic is torch.optim's single-tensor path with coupled weight decay
+ * g' = g + weight_decay * p; derived constants (1 - alpha, 1 - rho) are formed on the host in fp64.
+ *  _sgd_step      torch.optim.SGD(lr, momentum, weight_decay, nesterov) (optim_builder.py:15-17): buf = momentum*buf + g';
+ *                 d = g' + momentum*buf (nesterov) or buf; p -= lr*d.  Dampening 0.  momentum == 0: buf may be NULL, d = g'
+ *                 (nesterov != 0 is then an argument error, as in torch);
+ *  _rmsprop_step  torch.optim.RMSprop(lr, alpha, weight_decay) (optim_builder.py:13-14), not centered, no momentum:
+ *                 sq = alpha*sq + (1-alpha)*g'^2; p -= lr * g' / (sqrt(sq) + eps);
+ *  _adadelta_step torch.optim.Adadelta(lr, rho, weight_decay) (optim_builder.py:7-9): sq = rho*sq + (1-rho)*g'^2;
+ *                 delta = sqrt(acc + eps) / sqrt(sq + eps) * g'; acc = rho*acc + (1-rho)*delta^2; p -= lr*delta.
+ * All three are stepped where the reference steps its optimizer, trainer/train.py:50-52. */
+int t3d_sgd_step(float* p, const float* g, float* buf, long long n, double lr, double momentum, double weight_decay,
+                 int nesterov, long long step, double grad_scale, void* stream);
+int t3d_rmsprop_step(float* p, const float* g, float* sq, long long n, double lr, double alpha, double eps,
+                     double weight_decay, long long step, double grad_scale, void* stream);
+int t3d_adadelta_step(float* p, const float* g, float* sq, float* acc, long long n, double lr, double rho, double eps,
+                      double weight_decay, long long step, double grad_scale, void* stream);
 /* Divergence watch for the optimizer steps that follow (process-wide, like t3d_set_reduction_replicas): with a DEVICE
- * int64 word set (the caller initialises it to INT64_MAX), t3d_adamw_step does *word = min(*word, step) when it meets a
- * non-finite gradient element; NULL switches it off.  Serves the loss the reference's loop reads at train.py:57 -- after a
+ * int64 word set (the caller initialises it to INT64_MAX), every optimizer step of this header (t3d_adamw_step, t3d_sgd_step,
+ * t3d_rmsprop_step, t3d_adadelta_step) does *word = min(*word, step) when it meets a non-finite gradient element; NULL
+ * switches it off.  Serves the loss the reference's loop reads at train.py:57 -- after a
  * divergence `loss.item()` is NaN there, while the clamp-form ReLU6 of the 16-bit kernels can leave this path's loss
  * finite: the trainer reports NaN from the first watched step on, per step and identically on every rank (the gradient is
  * all-reduced before the optimizer reads it). */
