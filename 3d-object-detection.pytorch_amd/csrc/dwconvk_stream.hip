@@ -274,5 +274,6 @@ int t3d_dwk_fwd_stream(int dtype, const void* x, const t3d_prologue* pro, const 
   a.Wo = (W + 2 * pad - k) / stride + 1;
   if (dtype == T3D_F32) return launch_t<float>(a, k, stride, st);
   if (dtype == T3D_BF16) return launch_t<bf16_t>(a, k, stride, st);
+  if (dtype == T3D_F16) return launch_t<f16_t>(a, k, stride, st);       // inference forward (the 5x5 layers of the MobileNetV3 layouts)
   return T3D_ERR_ARG;
 }

@@ -625,8 +625,10 @@ int launch_v(GemmArgs& a, int KS, hipStream_t st) {
 template <int NT, int R>
 int launch_nt(GemmArgs& a, int KS, hipStream_t st, int deep_ku = 0) {
 #ifdef T3D_PW_F16
-  // fp16 storage: the plain inference forward only (BatchNorm + activation prologue, no gates, no materialising operand)
-  if (a.a2 || a.dgrad || a.z_out || a.per_sample || a.ps_stats || a.e_se || a.p2 || a.stats) return T3D_ERR_UNSUPPORTED;
+  // fp16 storage: the inference forward only (BatchNorm + activation prologue, optionally the squeeze-excite gate of the MobileNetV3
+  // layouts on the operand; no materialising operand, no statistics)
+  if (a.a2 || a.dgrad || a.z_out || a.per_sample || a.ps_stats || a.e_se || a.stats) return T3D_ERR_UNSUPPORTED;
+  if (a.p2) return launch_v<NT, R, false, true>(a, KS, st);
   return launch_v<NT, R, false, false>(a, KS, st);
 #else
   if (a.a2) return launch_v<NT, R, true, false, true>(a, KS, st);   // y-free data gradient

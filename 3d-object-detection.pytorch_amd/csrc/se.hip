@@ -663,3 +663,198 @@ extern "C" int t3d_se_bwd_weights(const float* m, const float* h, const float* d
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
+
+// ------------------------------------------------------------------ gate AFTER the activation: the whole backward as one launch
+// v = s * a, a = act(scale*y + shift), s = gate(mean_hw a).  The three-launch sequence (t3d_se_after_sums -> t3d_se_bwd_data ->
+// t3d_se_after_apply, elementwise.hip / above) reads dv and y from HBM twice and pays two dependent kernel boundaries.  The
+// gate's input gradient g[b,:] needs only sample b's own sums and the two FC matrices (only the FC WEIGHT gradients mix samples,
+// and those are issued separately from dq / dp), so here a workgroup owns one sample:
+//   pass 1   ds[c] = sum_hw dv*a            thread = (8-channel group, pixel slot); slot partials meet in LDS in slot order
+//   gate     dq = h_sigmoid'(q) ds,  dp = relu'(h) (dq W2),  g = (dp W1) / HW       (thread = output, as se_product above)
+//   pass 2   du = (s*dv + g) * act'(u) over the same plane -- at most 0.53 MB per sample in bf16 (672 x 14^2), so the re-read is
+//            served by L2 / Infinity Cache -- and sum(du), sum(du*y): slot partials summed in fp64 in slot order, ONE fp64 atomic
+//            per (workgroup, channel) into replica (workgroup % replicas), like the kernels around it.
+// Every workgroup streams both FC matrices (<= 1.8 MB fp32) out of L2: what the launch saves is one HBM pass over dv, y and two
+// launches, what it costs is that walk per SAMPLE instead of per four samples (se_slice_kernel) -- the engine takes it only at
+// the shapes where it measured faster.
+namespace {
+
+constexpr int SA_T = 1024;
+
+struct SeAfterArgs {
+  const void *dv, *y;
+  void* du;
+  const float *scale, *shift;
+  const float *w1, *w2, *h, *q, *s;
+  float *g, *dq, *dp;
+  double* stats;
+  int act, B, HW, C, R;
+  int nrep;
+  long long rstride;
+};
+
+// out[o] = sum_i in[i] * Wt[i*O + o];  in: LDS [I];  outputs walked in blocks of OP <= SA_T threads, the contraction split over
+// the SA_T / OP thread groups that the output width leaves free (partials through `part` [SA_T], added in group order).
+template <typename Fin>
+__device__ __forceinline__ void sa_matvec(const float* __restrict__ Wt, int I, int O, const float* in, float* part, Fin fin) {
+  const int t = threadIdx.x;
+  const int OP = min((O + 63) & ~63, SA_T);
+  const int ngrp = SA_T / OP, grp = t / OP, ol = t - grp * OP;
+  const int per = (I + ngrp - 1) / ngrp;
+  const int i0 = min(grp * per, I), i1 = min(i0 + per, I);
+  for (int ob = 0; ob < O; ob += OP) {
+    const int o = ob + ol;
+    const bool live = grp < ngrp && o < O;
+    float acc = 0.f;
+    if (live) {
+      int i = i0;
+      for (; i + 16 <= i1; i += 16) {              // sixteen independent weight loads in flight (a chain of L2 round trips)
+        float w[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) w[u] = Wt[(size_t)(i + u) * O + o];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc = fmaf(in[i + u], w[u], acc);
+      }
+      for (; i < i1; ++i) acc = fmaf(in[i], Wt[(size_t)i * O + o], acc);
+    }
+    if (ngrp > 1) {
+      __syncthreads();                               // `part` may still be read from the previous block / product
+      if (live && grp > 0) part[t] = acc;
+      __syncthreads();
+      if (live && grp == 0)
+        for (int g = 1; g < ngrp; ++g) acc += part[g * OP + ol];
+    }
+    if (live && grp == 0) fin(o, acc);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SA_T) void se_after_bwd_kernel(const SeAfterArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int C = a.C, R = a.R, HW = a.HW, CG = C / 8, t = threadIdx.x, b = blockIdx.x;
+  const int nslots = SA_T / CG;                      // >= 8 (C <= 1024)
+  float* red = lds;                                  // [nslots][C] slot partials
+  float* v0 = red + (size_t)nslots * C;              // [C] dq, later the gate s
+  float* v1 = v0 + C;                                // [C] g
+  float* vr = v1 + C;                                // [R] dp
+  float* part = vr + R;                              // [SA_T]
+  const int cgl = t % CG, slot = t / CG, c0 = cgl * 8;
+  const bool on = slot < nslots;
+  const T* __restrict__ dv = reinterpret_cast<const T*>(a.dv) + (size_t)b * HW * C;
+  const T* __restrict__ y = reinterpret_cast<const T*>(a.y) + (size_t)b * HW * C;
+  T* __restrict__ du = reinterpret_cast<T*>(a.du) + (size_t)b * HW * C;
+  float sc[8], sh[8], acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sc[j] = a.scale ? a.scale[c0 + j] : 1.f;
+    sh[j] = a.scale ? a.shift[c0 + j] : 0.f;
+    acc[j] = 0.f;
+  }
+  // ---- pass 1: ds[c] = sum_hw dv * act(scale*y + shift)
+  if (on) {
+    for (int hw = slot; hw < HW; hw += nslots) {
+      float v[8], d[8];
+      const size_t off = (size_t)hw * C + c0;
+      Vec8<T>::load(y + off, v);
+      Vec8<T>::load(dv + off, d);
+      act_affine_vec<8>(v, sc, sh, a.act);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = fmaf(d[j], v[j], acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[slot * C + c0 + j] = acc[j];
+  }
+  __syncthreads();
+  for (int c = t; c < C; c += SA_T) {
+    float ds = 0.f;
+    for (int k = 0; k < nslots; ++k) ds += red[k * C + c];
+    const size_t i = (size_t)b * C + c;
+    const float qq = a.q[i];
+    const float v = (qq > -3.f && qq < 3.f) ? ds * (1.f / 6.f) : 0.f;     // relu6 passes strictly inside
+    a.dq[i] = v;
+    v0[c] = v;
+  }
+  __syncthreads();
+  // ---- the gate's two products
+  sa_matvec(a.w2, C, R, v0, part, [&](int o, float s) {                  // dp = relu'(h) * (dq W2);  W2 is [C][R] = [I][O]
+    const float v = a.h[(size_t)b * R + o] > 0.f ? s : 0.f;
+    a.dp[(size_t)b * R + o] = v;
+    vr[o] = v;
+  });
+  __syncthreads();
+  const float inv = 1.f / (float)HW;
+  sa_matvec(a.w1, R, C, vr, part, [&](int o, float s) {                  // g = (dp W1) / HW;  W1 is [R][C] = [I][O]
+    const float gu = s * inv;                                            // every pixel of a receives dL/dm / HW
+    a.g[(size_t)b * C + o] = gu;
+    v1[o] = gu;
+  });
+  __syncthreads();
+  for (int c = t; c < C; c += SA_T) v0[c] = a.s[(size_t)b * C + c];
+  __syncthreads();
+  // ---- pass 2: du = (s*dv + g) * act'(u), sum(du), sum(du*y)
+  float gs[8], gg[8], s1[8], s2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    gs[j] = v0[c0 + j];
+    gg[j] = v1[c0 + j];
+    s1[j] = s2[j] = 0.f;
+  }
+  if (on) {
+    for (int hw = slot; hw < HW; hw += nslots) {
+      float d[8], yv[8];
+      const size_t off = (size_t)hw * C + c0;
+      Vec8<T>::load(dv + off, d);
+      Vec8<T>::load(y + off, yv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float da = fmaf(gs[j], d[j], gg[j]);
+        const float v = Vec8<T>::round(da * act_grad(yv[j] * sc[j] + sh[j], a.act));
+        d[j] = v;
+        s1[j] += v;
+        s2[j] = fmaf(v, yv[j], s2[j]);
+      }
+      Vec8<T>::store(du + off, d);
+    }
+  }
+  if (!a.stats) return;
+  double* st = a.stats + (size_t)(b % a.nrep) * a.rstride;
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    __syncthreads();                                 // (`red` of the previous round has been read)
+    if (on) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[slot * C + c0 + j] = which ? s2[j] : s1[j];
+    }
+    __syncthreads();
+    for (int c = t; c < C; c += SA_T) {
+      double v = 0.0;
+      for (int k = 0; k < nslots; ++k) v += (double)red[k * C + c];
+      atomicAdd(st + (size_t)which * C + c, v);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int t3d_se_after_bwd(int dtype, const void* dv, const void* y, const t3d_prologue* pro, const float* w1,
+                                const float* w2, const float* h, const float* q, const float* s, float* g, float* dq,
+                                float* dp, void* du, double* stats, int B, int HW, int C, int R, void* stream) {
+  if (!dv || !y || !w1 || !w2 || !h || !q || !s || !g || !dq || !dp || !du || B <= 0 || HW <= 0 || C <= 0 || R <= 0 || (C % 8))
+    return T3D_ERR_ARG;
+  if (C > 1024 || R > 1024) return T3D_ERR_UNSUPPORTED;
+  if (pro && pro->se) return T3D_ERR_UNSUPPORTED;
+  SeAfterArgs a{};
+  a.dv = dv; a.y = y; a.du = du; a.w1 = w1; a.w2 = w2; a.h = h; a.q = q; a.s = s; a.g = g; a.dq = dq; a.dp = dp;
+  a.stats = stats; a.B = B; a.HW = HW; a.C = C; a.R = R; a.act = T3D_ACT_NONE;
+  if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
+  a.nrep = g_t3d_reduce.nrep < 1 ? 1 : g_t3d_reduce.nrep;
+  a.rstride = g_t3d_reduce.nrep < 1 ? 0 : g_t3d_reduce.stats_stride;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (const int rc = t3d_fold_fallback(a.scale, st)) return rc;      // no derive prologue here: finalize as its own launch
+  const size_t lds = ((size_t)(SA_T / (C / 8)) * C + 2 * (size_t)C + R + SA_T) * sizeof(float);      // <= 48 KB
+  if (dtype == T3D_F32) T3D_LAUNCH(se_after_bwd_kernel<float>, dim3(B), dim3(SA_T), lds, st, a);
+  else if (dtype == T3D_BF16) T3D_LAUNCH(se_after_bwd_kernel<bf16_t>, dim3(B), dim3(SA_T), lds, st, a);
+  else return T3D_ERR_ARG;
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}

@@ -103,6 +103,7 @@ SIGNATURES = {
     't3d_se_bwd_weights': [_P] * 8 + [_I] * 3 + [_P],
     't3d_se_after_sums': [_I, _P, _P, _PP, _P, _I, _I, _I, _P],
     't3d_se_after_apply': [_I, _P, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _P],
+    't3d_se_after_bwd': [_I, _P, _P, _PP] + [_P] * 10 + [_I] * 4 + [_P],
     't3d_set_reduction_replicas': [_I, _L],
     't3d_set_workspace': [_P, _L],
     't3d_set_main_workspace': [_P, _L],

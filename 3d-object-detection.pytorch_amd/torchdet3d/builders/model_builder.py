@@ -8,15 +8,21 @@ reference's).  Differences a caller can observe:
     optimizer built by `build_optimizer` is a single fused update and data-parallel training all-reduces one
     buffer; `named_parameters()` therefore has one entry, `state_dict()` keeps the per-layer names;
   * the forward runs on the GPU only ('--device cuda'); there is no CPU fallback;
-  * extra model names: 'mobilenetv2' (north-star throughput model) and 'resnet50' (BASELINE config 4; standard torchvision
-    architecture, models/resnet.py).  The timm / efficientnet-lite names of the reference need un-vendored third-party
-    packages and are not built.
+  * model names: of the reference's six, 'mobilenetv3_large', 'mobilenetv3_small' and 'mobilenetv3_large_21k' (its default
+    config's model: timm's mobilenetv3_large_100 restated in models/arch.py -- timm is installed nowhere this project is
+    built or tested, so the layout, key names and initialisation are UNPINNED against timm itself; the parameter count and
+    everything shared with the reference's own class are pinned).  'efficientnet-lite0/1/2' are not built: no source of the
+    efficientnet_lite_pytorch package exists to restate, and they need TF-"same" asymmetric padding, BatchNorm eps 1e-3 and
+    stochastic depth in training (an RNG contract of its own).  Extra names: 'mobilenetv2' (north-star throughput model) and
+    'resnet50' (BASELINE config 4; standard torchvision architecture, models/resnet.py).
   * `regressors`, `cls_fc`, `sigmoid` (model_builder.py:79-87) are views onto the flat buffer, `extract_features`
     (mobilenetv3.py:199-203) and `_glob_feature_vector` (:96-110) are callable but inference-only: training goes
     through `forward`, whose whole graph is one autograd node;
   * a train-mode model called under `torch.no_grad()` behaves like the reference's: batch statistics, running
     estimates updated, dropout applied -- only the activations are not kept for a backward.
-Config keys read: model.name, model.num_classes, model.pretrained (ignored: no network), model.load_weights,
+Config keys read: model.name, model.num_classes, model.pretrained (never touches the network: 'mobilenetv3_large_21k' loads
+$TORCH_HOME/checkpoints/mobilenetv3_large_21k_imagenet.pth -- the file the reference's init_pretrained_weights caches -- when
+it exists and says so in one line when it does not; ignored for the other names), model.load_weights,
 model.storage_dtype ('f32' default for parity | 'bf16' throughput mode), model.eval_storage_dtype (storage precision of
 eval-mode forwards; default 'f32' also for a 'bf16' model, so that inference outputs meet the 1e-4 parity bound; 'f16': fp16
 activation storage, the fast option that is INSIDE the 1e-3 3-D-IoU / ADD bounds for mobilenetv2 (keypoints 1.7e-4, 2.3x the
@@ -134,8 +140,9 @@ class ModelWrapper(nn.Module):
         if not eval_storage_dtype:
             eval_storage_dtype = 'f32' if self.storage_dtype == torch.bfloat16 else None
         # 'f16' (round 4): fp16 activation storage for inference -- bf16's bytes and speed with three more mantissa bits at every
-        # MFMA operand; exists for the squeeze-excite-free backbones (mobilenetv2), anything else falls back to 'f32'
-        if eval_storage_dtype in ('f16', torch.float16) and name != 'mobilenetv2':
+        # MFMA operand; served for mobilenetv2 and mobilenetv3_large_21k (whose 5x5 depthwise and gated 1x1 forwards exist in fp16),
+        # anything else falls back to 'f32'
+        if eval_storage_dtype in ('f16', torch.float16) and name not in ('mobilenetv2', 'mobilenetv3_large_21k'):
             eval_storage_dtype = 'f32'
         self.eval_storage_dtype = (None if not eval_storage_dtype else
                                    torch.bfloat16 if eval_storage_dtype in ('bf16', torch.bfloat16) else
@@ -306,6 +313,26 @@ def _init_distributed():
         dist.init_process_group('gloo')
 
 
+PRETRAINED_CACHED = ('mobilenetv3_large_21k',)      # names whose `pretrained=True` looks for the reference's cached file
+
+
+def _torch_home():
+    """mobilenetv3.py:243-255."""
+    return os.path.expanduser(os.getenv('TORCH_HOME', os.path.join(os.getenv('XDG_CACHE_HOME', '~/.cache'), 'torch')))
+
+
+def _load_cached_pretrained(model, name):
+    """`init_pretrained_weights(model, key=name, extra_prefix='model.')` (model_builder.py:68-69, mobilenetv3.py:234-271)
+    WITHOUT its download: the cached checkpoint is loaded when it is there (bare timm keys -> `model.*`; name or shape
+    mismatches such as the checkpoint's `classifier.*` are dropped), otherwise the model keeps its initialisation."""
+    cached = os.path.join(_torch_home(), 'checkpoints', name + '_imagenet.pth')
+    if os.path.isfile(cached):
+        load_pretrained_weights(model, cached, extra_prefix='model.')
+        return True
+    print(f'** model.pretrained: "{cached}" not found and nothing is downloaded; training starts from the initialisation')
+    return False
+
+
 def build_model(config, export_mode=False, weights_path=''):
     _init_distributed()
     if config.data_parallel and config.data_parallel.use_parallel and \
@@ -320,6 +347,8 @@ def build_model(config, export_mode=False, weights_path=''):
     weights = config.model.load_weights or weights_path
     if weights:
         load_pretrained_weights(model, weights)
+    elif config.model.pretrained and not export_mode and name in PRETRAINED_CACHED:
+        _load_cached_pretrained(model, name)
     norm = getattr(getattr(config, 'data', None), 'normalization', None)
     if norm:
         model.set_input_normalization(norm.mean, norm.std)

@@ -39,7 +39,22 @@ MAIN_WORKSPACE_BYTES = 16 << 20
 YFREE_MIN_ELEMS = int(os.environ.get('T3D_YFREE_MIN', 8 << 20))
 YFREE_MAX_K = int(os.environ.get('T3D_YFREE_MAX_K', 112))     # widest narrow side the y-free backward is used for (the K x K Gram terms); round 6: 96 -> 112 takes MobileNetV3-large's two 112 -> 672 expansions at 14x14 (7.59-7.65 -> 7.43 ms per step; 160, the 7x7 stage: 7.53)
 HOOK_MIN = 1 << 20              # gradient-exchange granularity (elements): parallel.GradSync's bucket size
+SE_AFTER_FUSED = None            # gate-after backward: None = choose by shape (Net._se_after_fused)
 HOOK_ON_SIDE = True              # (round 3: the gradient exchange is issued from the second stream; the other order stalled the main one)
+
+
+def _se_after_fused_by_shape(dt, B, HW, C, R):
+    """Where the one-launch gate-after backward (t3d_se_after_bwd) measured faster than the three-launch sequence by more
+    than the spread of the repetitions (tools/time_se_after.py; table in DESIGN.md section 4; bf16 and fp32 storage gave the
+    same verdicts).  A workgroup per sample walks both FC matrices on its own: with the narrow gates (72 x 24, 120 x 32)
+    that walk is short and the launch won at every measured batch (8 ... 256); with the wide ones (480 x 120 ... 960 x 240)
+    it needs enough samples and pixels to pay for it -- it won from 16 samples and B*HW >= 1024 on, lost or tied below.
+    Outside the measured range (fewer than 8 samples) the sequence stays."""
+    if B < 8:
+        return False
+    if C * R <= 4096:
+        return True
+    return B >= 16 and B * HW >= 1024
 
 
 class _BN:
@@ -108,6 +123,13 @@ class Net:
         self.pooling_mode, self.pool = pooling_mode, N.POOL[pooling_mode]
         self.arch = Arch(name)
         self.name, self.num_classes = name, num_classes
+        # timm's head ('conv_bias'): the network's own global pool is an AVERAGE in front of conv_head; the wrapper's
+        # `_glob_feature_vector` then pools the resulting 1x1 map (model_builder.py:96-110, kept literal): 'avg' and 'max' are
+        # the identity there, 'avg+max' adds the map to itself
+        self.feat_gain = 1.0
+        if self.arch.head == 'conv_bias':
+            self.pool = N.POOL['avg']
+            self.feat_gain = 2.0 if pooling_mode == 'avg+max' else 1.0
         self.device = torch.device(device)
         # torch.float16: INFERENCE storage only (the forward kernels exist in fp16, csrc/pwconv_stream_f16.hip etc.; gradients
         # keep bf16's range) -- three more mantissa bits than bf16 at every MFMA operand, same bytes
@@ -236,7 +258,11 @@ class Net:
     def reset_parameters(self, seed=None):
         """Initialisation of the reference: mobilenetv3.py:205-218 for the backbone (conv N(0, sqrt(2/(k*k*Cout))),
         BN 1/0, Linear N(0, .01)/0), PyTorch's default Linear init for the heads added afterwards by
-        ModelWrapper (model_builder.py:79-85)."""
+        ModelWrapper (model_builder.py:79-85).  Key scheme 'timm' (everything under `model.`): timm's
+        `efficientnet_init_weights` as remembered, unpinned like the key names -- conv N(0, sqrt(2/fan_out)) with
+        fan_out = k*k*Cout / groups (a depthwise conv gets sqrt(2/k^2)), the squeeze-excite 1x1 convs included, zero biases,
+        BN 1/0."""
+        timm = getattr(getattr(self.arch, 'keys', None), 'scheme', None) == 'timm'
         gen = torch.Generator(device='cpu')
         if seed is not None:
             gen.manual_seed(seed)
@@ -247,7 +273,8 @@ class Net:
                 bound = 1.0 / math.sqrt(self.arch.feat_c)
                 v = (torch.rand(s, generator=gen) * 2 - 1) * bound
             elif len(s) == 4:
-                v = torch.randn(s, generator=gen) * math.sqrt(2.0 / (s[2] * s[3] * s[0]))
+                groups = s[0] if (timm and s[1] == 1 and s[2] > 1) else 1
+                v = torch.randn(s, generator=gen) * math.sqrt(2.0 * groups / (s[2] * s[3] * s[0]))
             elif len(s) == 2:
                 v = torch.randn(s, generator=gen) * 0.01
             elif k.endswith('.bias'):
@@ -353,8 +380,9 @@ class Net:
             # deep-contraction kernel streams them), keyed by the plain copy's address: forward (K, N), data gradient (N, K)
             self._frag = {}
             lib = N.lib()
+            fp32_only = self._fp32_1x1()
             for k, (s, kind) in self.shapes.items():
-                if kind != 'param' or len(s) != 4 or s[2] != 1:
+                if kind != 'param' or len(s) != 4 or s[2] != 1 or k in fp32_only:
                     continue
                 n, kk = s[0], s[1]
                 src = self.p[k]
@@ -379,7 +407,7 @@ class Net:
         if getattr(self, '_se_pack_desc', None) is None:
             rows = []
             for k, (s, kind) in self.shapes.items():
-                if kind == 'param' and len(s) == 2 and ('.fc.0.weight' in k or '.fc.2.weight' in k):
+                if kind == 'param' and k in self._se_weights():
                     self.wt[k] = self._buf('wt:' + k, (s[1], s[0]), torch.float32)
                     rows.append([self.p[k].data_ptr(), 0, self.wt[k].data_ptr(), s[0], s[1], 0, 0])
             self._se_pack_desc = torch.tensor(rows, dtype=torch.int64, device=self.device) if rows else False
@@ -393,18 +421,29 @@ class Net:
         # stem: [C,3,3,3] -> [C,32] patch-row weights (columns 27..31 zero)
         c0 = self.arch.stem_c
         w32 = self._buf('stem32', (c0, 32), torch.float32)
-        N.call('t3d_copy_cols', N.ptr(self.p['features.0.0.weight']), N.ptr(w32), c0, 27, 32, st)
+        N.call('t3d_copy_cols', N.ptr(self.p[self.arch.keys.stem_w]), N.ptr(w32), c0, 27, 32, st)
         if self.dt == N.F32:
             self.w['stem'] = w32
         else:
             self.w['stem'] = self._buf('w:stem', (c0, 32))
             N.call('t3d_pack_weight', self.dt, N.ptr(w32), N.ptr(self.w['stem']), c0, 32, 0, st)
-        if self.arch.classifier:
-            wc = self.p['classifier.0.weight']
+        if self.arch.head:
+            wc = self.p[self.arch.keys.head_w]       # Linear [F,K] or 1x1 conv [F,K,1,1]: the same fp32 matrix
             self.wt['classifier'] = self._buf('wt:cls', (wc.shape[1], wc.shape[0]), torch.float32)
             N.call('t3d_pack_weight', N.F32, N.ptr(wc), N.ptr(self.wt['classifier']), wc.shape[0], wc.shape[1], 1, st)
         self._packed_dirty = False
         self._packed_version = self.flat._version
+
+    def _se_weights(self):
+        """Keys of the squeeze-excite FC matrices (fp32; Linear [O,I] or 1x1 conv [O,I,1,1])."""
+        keys = getattr(self.arch, 'keys', None)
+        return frozenset(k for bk in (keys.blocks if keys else ()) if bk.se for k in (bk.se_w1, bk.se_w2))
+
+    def _fp32_1x1(self):
+        """1x1-conv-shaped parameters that are NOT activations-dtype pointwise layers: they stay fp32 and have their own packing
+        (timm's squeeze-excite convs, conv_head)."""
+        a = self.arch
+        return self._se_weights() | (frozenset((a.keys.head_w,)) if a.head == 'conv_bias' else frozenset())
 
     def _pack_extra(self, st):
         """Hook: weight layouts of architectures with more than 1x1 / depthwise / stem convolutions (models/resnet.py)."""
@@ -545,7 +584,7 @@ class Net:
     # ------------------------------------------------------------------ forward
     def _main_scratch(self, on):
         # split-contraction scratch of the fp32 classifier products (main stream; include/t3d.h: t3d_set_main_workspace)
-        if on and self.arch.classifier:
+        if on and self.arch.head:
             ws = self._buf('workspace_main', (MAIN_WORKSPACE_BYTES,), torch.uint8)
             N.call('t3d_set_main_workspace', N.ptr(ws), MAIN_WORKSPACE_BYTES)
         else:
@@ -586,14 +625,28 @@ class Net:
 
         # ---- classifier Linear + BatchNorm1d + h_swish, MobileNetV3 only (mobilenetv3.py:191-195)
         f, fpro = pooled, None
-        if a.classifier:
-            bnc = self.bns['classifier.1']
+        if a.head == 'linear_bn':
+            bnc = self.bns[a.keys.head_bn]
             yc = self._buf('y:cls', (B, a.classifier), torch.float32)
-            N.call('t3d_pwconv_fwd', N.F32, N.ptr(pooled), None, N.ptr(self.p['classifier.0.weight']),
-                   N.ptr(self.p['classifier.0.bias']), N.ptr(yc), self._st(bnc), B, 1, a.last_c, a.classifier, st)
+            N.call('t3d_pwconv_fwd', N.F32, N.ptr(pooled), None, N.ptr(self.p[a.keys.head_w]),
+                   N.ptr(self.p[a.keys.head_b]), N.ptr(yc), self._st(bnc), B, 1, a.last_c, a.classifier, st)
             fpro = self._bn_fwd(bnc, B, 'hswish')
             self._settle_f(bnc)
             f = yc
+        elif a.head == 'conv_bias':
+            # timm's conv_head on the pooled vector: u = W pooled + b (fp32), f = h_swish(u) applied by the head kernels on load
+            Fc = a.classifier
+            yc = self._buf('y:cls', (B, Fc), torch.float32)
+            N.call('t3d_pwconv_fwd', N.F32, N.ptr(pooled), None, N.ptr(self.p[a.keys.head_w]),
+                   N.ptr(self.p[a.keys.head_b]), N.ptr(yc), None, B, 1, a.last_c, Fc, st)
+            f, fpro = yc, N.prologue(self._const(Fc, 1.0), self._const(Fc, 0.0), None, 'hswish', False)
+            sv['head_u'], sv['head_pro'] = yc, fpro
+            if self.feat_gain != 1.0:
+                # pooling_mode 'avg+max' over the 1x1 map: avg + max = twice the value
+                f = self._buf('f:gain', (B, Fc), torch.float32)
+                N.call('t3d_bn_apply', N.F32, N.ptr(yc), fpro, None, N.ptr(f), B, Fc, st)
+                N.call('t3d_bn_apply', N.F32, N.ptr(f), None, N.ptr(f), N.ptr(f), B, Fc, st)      # f + f, in place
+                fpro = None
         # ---- heads (model_builder.py:137-144)
         ncls = self.num_classes
         keep = self.persistent_outputs and not all_heads
@@ -692,7 +745,7 @@ class Net:
         # kernels was measured slower, DESIGN.md finding 13; tools/scratch/pruned_r4 has what is left of it)
         Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
         M = B * Ho * Wo
-        bn0 = self.bns['features.0.1']
+        bn0 = self.bns[a.keys.stem_bn]
         y0 = self._buf('y:stem', (M, a.stem_c))
         col = self._buf('col', (M, 32))
         if u8:
@@ -712,11 +765,10 @@ class Net:
                 sv.setdefault('taps', {})[i + 1] = self._resolve(cur)
 
         # ---- last 1x1 conv (mobilenetv3.py:118-123,188) + global average pool (model_builder.py:96-110)
-        ln = a.last_name
-        bnl = self.bns[ln + '.1']
+        bnl = self.bns[a.keys.last_bn]
         M = cur.B * cur.H * cur.W
         yl = self._buf('y:last', (M, a.last_c))
-        self._pw_from(cur, self.w[ln + '.0.weight'], yl, bnl, M, cur.H * cur.W, cur.C, a.last_c)
+        self._pw_from(cur, self.w[a.keys.last_w], yl, bnl, M, cur.H * cur.W, cur.C, a.last_c)
         prol = self._bn_fwd(bnl, M, a.last_act)
         pooled = self._buf('pooled', (B, a.last_c), torch.float32)
         sv.update(last_in=cur, yl=yl, prol=prol, pooled=pooled, HWl=cur.H * cur.W, bnl=bnl)
@@ -792,31 +844,31 @@ class Net:
 
     def _block_fwd(self, i, blk, x, sv):
         st, dt = N.stream(), self.dt
-        p = f'features.{i + 1}.conv'
+        bk = self.arch.keys.blocks[i]
         B, H, W = x.B, x.H, x.W
         if self._fused_eval_ok(blk, x):
-            bn1, bn2, bn3 = self.bns[p + '.1'], self.bns[p + '.4'], self.bns[p + '.8']
+            bn1, bn2, bn3 = self.bns[bk.bn1], self.bns[bk.bn2], self.bns[bk.bn3]
             z = self._buf(f'z:{i}', (B * H * W, blk.cout))
             act = N.ACT[blk.act] if isinstance(blk.act, str) else blk.act
-            N.call('t3d_ir_block_eval', N.ptr(x.t), N.ptr(self.w[p + '.0.weight']), N.ptr(bn1.scale), N.ptr(bn1.shift),
-                   act, N.ptr(self.p[p + '.3.weight']), N.ptr(bn2.scale), N.ptr(bn2.shift), act,
-                   N.ptr(self.w[p + '.7.weight']), N.ptr(bn3.scale), N.ptr(bn3.shift), int(bool(blk.res)), N.ptr(z),
+            N.call('t3d_ir_block_eval', N.ptr(x.t), N.ptr(self.w[bk.exp_w]), N.ptr(bn1.scale), N.ptr(bn1.shift),
+                   act, N.ptr(self.p[bk.dw_w]), N.ptr(bn2.scale), N.ptr(bn2.shift), act,
+                   N.ptr(self.w[bk.pw_w]), N.ptr(bn3.scale), N.ptr(bn3.shift), int(bool(blk.res)), N.ptr(z),
                    B, H, W, blk.cin, blk.cexp, blk.cout, st,
                    nbytes=B * H * W * (2 * blk.cin + 4 * blk.cexp + 2 * blk.cout) * self.esz)
             return _Src(z, None, B, H, W, blk.cout, raw=None, bn=bn3, gpro=None)
         if self._expdw_ok(blk, x):
             # inference, 16-bit storage, the 112x112 .. 28x28 blocks: expand 1x1 + BatchNorm + activation + depthwise 3x3 in ONE
             # launch, the expanded tensor never leaves LDS (csrc/expdw_fwd.hip; DESIGN.md finding 40)
-            bn1, bn2, bn3 = self.bns[p + '.1'], self.bns[p + '.4'], self.bns[p + '.8']
+            bn1, bn2, bn3 = self.bns[bk.bn1], self.bns[bk.bn2], self.bns[bk.bn3]
             Ho, Wo = (H + 2 - 3) // blk.s + 1, (W + 2 - 3) // blk.s + 1
             M2 = B * Ho * Wo
             y2 = self._buf(f'y2:{i}', (M2, blk.cexp))
-            N.call('t3d_expdw_fwd', dt, N.ptr(x.t), N.ptr(self.w[p + '.0.weight']), N.ptr(bn1.scale), N.ptr(bn1.shift),
-                   N.ACT[blk.act] if isinstance(blk.act, str) else blk.act, N.ptr(self.p[p + '.3.weight']), None, N.ptr(y2), None,
+            N.call('t3d_expdw_fwd', dt, N.ptr(x.t), N.ptr(self.w[bk.exp_w]), N.ptr(bn1.scale), N.ptr(bn1.shift),
+                   N.ACT[blk.act] if isinstance(blk.act, str) else blk.act, N.ptr(self.p[bk.dw_w]), None, N.ptr(y2), None,
                    B, H, W, blk.cin, blk.cexp, blk.s, st, nbytes=(B * H * W * blk.cin + M2 * blk.cexp) * self.esz)
             pro2 = self._bn_fwd(bn2, M2, blk.act)
             y3 = self._buf(f'y3:{i}', (M2, blk.cout))
-            wd, wp = self._wsel(self.w[p + '.7.weight'])
+            wd, wp = self._wsel(self.w[bk.pw_w])
             N.call('t3d_pwconv_fwd', wd, N.ptr(y2), pro2, wp, None, N.ptr(y3), None, M2, Ho * Wo, blk.cexp, blk.cout, st,
                    nbytes=M2 * (blk.cexp + blk.cout) * self.esz)
             out = _Src(y3, self._bn_fwd(bn3, M2, 'none'), B, Ho, Wo, blk.cout, raw=y3, bn=bn3, gpro=None)
@@ -829,18 +881,16 @@ class Net:
         rec = dict(x=x)
         src = x
         if blk.expand:                                                    # mobilenetv3.py:146-150
-            bn1 = self.bns[p + '.1']
+            bn1 = self.bns[bk.bn1]
             M = B * H * W
             y1 = self._buf(f'y1:{i}', (M, blk.cexp))
-            self._pw_from(x, self.w[p + '.0.weight'], y1, bn1, M, H * W, blk.cin, blk.cexp)
+            self._pw_from(x, self.w[bk.exp_w], y1, bn1, M, H * W, blk.cin, blk.cexp)
             pro1 = self._bn_fwd(bn1, M, blk.act)
             src = _Src(y1, pro1, B, H, W, blk.cexp, raw=y1, bn=bn1, gpro=pro1)
             rec['s1'] = src
-            dwn, bnn, pwn, bn3n = p + '.3.weight', p + '.4', p + '.7.weight', p + '.8'
-        else:                                                             # mobilenetv3.py:133-144
-            dwn, bnn, pwn, bn3n = p + '.0.weight', p + '.1', p + '.4.weight', p + '.5'
-        se_after = bool(blk.se and not blk.expand)         # gate AFTER the activation (mobilenetv3.py:138-140)
-        sen = ((p + '.3') if se_after else (p + '.5')) if blk.se else None
+        dwn, bnn, pwn, bn3n = bk.dw_w, bk.bn2, bk.pw_w, bk.bn3       # (no-expand layout: mobilenetv3.py:133-144)
+        se_after = blk.se_after         # gate AFTER the activation (mobilenetv3.py:138-140; every block of the timm layout)
+        sen = bk if blk.se else None
         # depthwise k x k (mobilenetv3.py:136,152)
         pad = (blk.k - 1) // 2
         Ho, Wo = (H + 2 * pad - blk.k) // blk.s + 1, (W + 2 * pad - blk.k) // blk.s + 1
@@ -868,9 +918,9 @@ class Net:
                       s=self._buf(f'se_s:{i}', (B, C), torch.float32), name=sen, HW=Ho * Wo, after=True, pro2n=pro2)
             ones, zeros = self._const(C, 1.0), self._const(C, 0.0)
             self._pool_exact(False)
-            N.call('t3d_se_fwd_fused', N.ptr(pooled), N.ptr(ones), N.ptr(zeros), N.ptr(self.wt[sen + '.fc.0.weight']),
-                   N.ptr(self.p[sen + '.fc.0.bias']), N.ptr(self.wt[sen + '.fc.2.weight']),
-                   N.ptr(self.p[sen + '.fc.2.bias']), N.ptr(se['m']), N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']),
+            N.call('t3d_se_fwd_fused', N.ptr(pooled), N.ptr(ones), N.ptr(zeros), N.ptr(self.wt[sen.se_w1]),
+                   N.ptr(self.p[sen.se_b1]), N.ptr(self.wt[sen.se_w2]),
+                   N.ptr(self.p[sen.se_b2]), N.ptr(se['m']), N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']),
                    B, C, R, 1, st)
             pro2 = self._pro(bn2, blk.act, se['s'], True)
             rec['se'] = se
@@ -880,9 +930,9 @@ class Net:
                       h=self._buf(f'se_h:{i}', (B, R), torch.float32), q=self._buf(f'se_q:{i}', (B, C), torch.float32),
                       s=self._buf(f'se_s:{i}', (B, C), torch.float32), name=sen, HW=Ho * Wo)
             self._pool_exact(True)
-            N.call('t3d_se_fwd_fused', N.ptr(gap), N.ptr(bn2.scale), N.ptr(bn2.shift), N.ptr(self.wt[sen + '.fc.0.weight']),
-                   N.ptr(self.p[sen + '.fc.0.bias']), N.ptr(self.wt[sen + '.fc.2.weight']),
-                   N.ptr(self.p[sen + '.fc.2.bias']), N.ptr(se['m']), N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']),
+            N.call('t3d_se_fwd_fused', N.ptr(gap), N.ptr(bn2.scale), N.ptr(bn2.shift), N.ptr(self.wt[sen.se_w1]),
+                   N.ptr(self.p[sen.se_b1]), N.ptr(self.wt[sen.se_w2]),
+                   N.ptr(self.p[sen.se_b2]), N.ptr(se['m']), N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']),
                    B, C, R, Ho * Wo, st)
             pro2 = self._pro(bn2, blk.act, se['s'], False)                # SE before the activation (:155-156)
             rec['se'] = se
@@ -946,8 +996,8 @@ class Net:
 
     def _se_wgrad(self, se, sen, dq, dp, B, C, R):
         # FC weight / bias gradients of a squeeze-excite gate: off the data-gradient chain, on the weight-gradient stream
-        self._wgrad(N.ptr(se['m']), N.ptr(se['h']), N.ptr(dq), N.ptr(dp), N.ptr(self.g[sen + '.fc.0.weight']),
-                    N.ptr(self.g[sen + '.fc.0.bias']), N.ptr(self.g[sen + '.fc.2.weight']), N.ptr(self.g[sen + '.fc.2.bias']),
+        self._wgrad(N.ptr(se['m']), N.ptr(se['h']), N.ptr(dq), N.ptr(dp), N.ptr(self.g[sen.se_w1]),
+                    N.ptr(self.g[sen.se_b1]), N.ptr(self.g[sen.se_w2]), N.ptr(self.g[sen.se_b2]),
                     B, C, R, entry='t3d_se_bwd_weights')
 
     def _fork_side(self):
@@ -1010,24 +1060,46 @@ class Net:
         F = a.feat_c
         dpre = self._buf('dpre', (B, 18), torch.float32)
         df = self._buf('df', (B, F), torch.float32)
-        bnc = self.bns['classifier.1'] if a.classifier else None
+        bnc = self.bns[a.keys.head_bn] if a.head == 'linear_bn' else None
+        hstat = None
+        if a.head == 'conv_bias':
+            # sum_b du of conv_head's pre-activation gradient (its bias gradient), fp64 like a BatchNorm's backward sums
+            hstat = self._buf('head_stats', (2 * F,), torch.float64, zgroup='bwd')
+            self._replicas(1)
         N.call('t3d_head_bwd', N.ptr(sv['f']), sv['fpro'], N.ptr(sv['cats']), N.ptr(self.wreg),
                N.ptr(self.p['cls_fc.1.weight']), N.ptr(sv['mask']), N.ptr(sv['kp']), N.ptr(dkp), N.ptr(dlogits),
-               N.ptr(dpre), N.ptr(df), self._bst(bnc) if bnc else None, None, None, None, None, B, F, ncls, st)
+               N.ptr(dpre), N.ptr(df), self._bst(bnc) if bnc else (N.ptr(hstat) if sv['fpro'] is not None else None),
+               None, None, None, None, B, F, ncls, st)
         # the heads' weight gradients are leaves: second stream (idle at this point of the step)
         self._wgrad(N.ptr(sv['f']), sv['fpro'], N.ptr(sv['cats']), N.ptr(sv['mask']), N.ptr(dpre), N.ptr(dlogits),
                     N.ptr(self.dwreg), N.ptr(self.dbreg), N.ptr(self.g['cls_fc.1.weight']), N.ptr(self.g['cls_fc.1.bias']),
                     B, F, ncls, entry='t3d_head_bwd_weights')
         dpooled = df
-        if a.classifier:
+        if a.head == 'conv_bias':
+            # df: gradient at conv_head's pre-activation u (head_bwd applied h_swish'(u)) -- or, with the doubled features of
+            # pooling_mode 'avg+max', at the features: h_swish' then goes on here and the factor 2 rides on the backward affine
+            yc, pooled, Fc = sv['head_u'], sv['pooled'], a.classifier
+            if sv['fpro'] is None:
+                du = self._buf('dhead_u', (B, Fc), torch.float32)
+                N.call('t3d_bn_act_bwd', N.F32, N.ptr(df), N.ptr(yc), sv['head_pro'], N.ptr(du), N.ptr(hstat), B, Fc, st)
+                df = du
+            gain, zeros = self._const(Fc, self.feat_gain), self._const(Fc, 0.0)
+            bb = N.bnbwd(gain, zeros, zeros, False)         # dy = gain * du
+            self._wgrad(N.F32, N.ptr(df), N.ptr(yc), bb, N.ptr(pooled), None, N.ptr(self.g[a.keys.head_w]), B, 1, a.last_c, Fc)
+            N.call('t3d_bn_bias_grad', N.ptr(hstat), N.ptr(hstat), Fc, float(B), N.ptr(gain), N.ptr(zeros), N.ptr(zeros),
+                   N.ptr(self.g[a.keys.head_b]), st)
+            dpooled = self._buf('dpooled', (B, a.last_c), torch.float32)
+            N.call('t3d_pwconv_dgrad', N.F32, N.ptr(df), N.ptr(yc), bb, N.ptr(self.wt['classifier']), None, None,
+                   None, N.ptr(dpooled), None, None, B, 1, a.last_c, Fc, st)
+        elif a.head == 'linear_bn':
             bb = self._bn_bwd(bnc)
             self._settle_b(bnc)
             yc, pooled = sv['f'], sv['pooled']
             self._wgrad(N.F32, N.ptr(df), N.ptr(yc), bb, N.ptr(pooled), None,
-                        N.ptr(self.g['classifier.0.weight']), B, 1, a.last_c, a.classifier)
+                        N.ptr(self.g[a.keys.head_w]), B, 1, a.last_c, a.classifier)
             # bias gradient = sum_b dy = alpha*sum(dz) + beta*sum(y) + B*gamma (exactly 0 in exact arithmetic)
             N.call('t3d_bn_bias_grad', N.ptr(bnc.stats), self._bst(bnc), a.classifier, float(B), N.ptr(bnc.alpha),
-                   N.ptr(bnc.bbeta), N.ptr(bnc.gammac), N.ptr(self.g['classifier.0.bias']), st)
+                   N.ptr(bnc.bbeta), N.ptr(bnc.gammac), N.ptr(self.g[a.keys.head_b]), st)
             dpooled = self._buf('dpooled', (B, a.last_c), torch.float32)
             N.call('t3d_pwconv_dgrad', N.F32, N.ptr(df), N.ptr(yc), bb, N.ptr(self.wt['classifier']), None, None,
                    None, N.ptr(dpooled), None, None, B, 1, a.last_c, a.classifier, st)
@@ -1042,8 +1114,8 @@ class Net:
         """From the gradient at the pooled feature vector back to the stem (MobileNet layouts; models/resnet.py overrides)."""
         a, st, dt, B = self.arch, N.stream(), self.dt, sv['B']
         # ---- pool + last conv
-        ln = a.last_name
-        bnl = self.bns[ln + '.1']
+        lw = a.keys.last_w
+        bnl = self.bns[a.keys.last_bn]
         x = sv['last_in']
         M, HW = B * sv['HWl'], sv['HWl']
         dzl = self._buf('dz:last', (M, a.last_c))
@@ -1054,15 +1126,15 @@ class Net:
         # themselves, the data gradient publishes them (issued the other way round the step is 0.27 ms slower)
         def last_wgrad():
             self._wgrad(dt, N.ptr(dzl), N.ptr(sv['yl']), bb, N.ptr(x.t), x.pro,
-                        N.ptr(self.g[ln + '.0.weight']), M, HW, x.C, a.last_c, nbytes=M * (x.C + a.last_c) * self.esz,
+                        N.ptr(self.g[lw]), M, HW, x.C, a.last_c, nbytes=M * (x.C + a.last_c) * self.esz,
                         ro=bnl)
         last_wgrad()
-        dz = self._pw_dgrad(dzl, sv['yl'], bb, self.wt[ln + '.0.weight'], x, None, M, HW, x.C, a.last_c, 'dz:lastin', bnl)
+        dz = self._pw_dgrad(dzl, sv['yl'], bb, self.wt[lw], x, None, M, HW, x.C, a.last_c, 'dz:lastin', bnl)
 
-        self._maybe_hook(self.offsets[ln + '.0.weight'][0])
+        self._maybe_hook(self.offsets[lw][0])
         for rec in reversed(sv['blocks']):
             dz = self._block_bwd(rec, dz)
-            self._maybe_hook(self.offsets[f"features.{rec['idx'] + 1}.conv.0.weight"][0])
+            self._maybe_hook(self.offsets[a.keys.blocks[rec['idx']].first][0])
 
         # ---- stem weight gradient
         s0 = sv['stem']
@@ -1074,7 +1146,7 @@ class Net:
                     M, s0.H * s0.W, 32, a.stem_c, nbytes=M * (32 + a.stem_c) * self.esz)
         self._flush_dw()
         self._join_side()
-        N.call('t3d_copy_cols', N.ptr(dw32), N.ptr(self.g['features.0.0.weight']), a.stem_c, 32, 27, st)
+        N.call('t3d_copy_cols', N.ptr(dw32), N.ptr(self.g[a.keys.stem_w]), a.stem_c, 32, 27, st)
 
     def _pw_dgrad(self, dz, y, bb, wt, x, residual, M, HW, K, Nn, tag, bn=None):
         """Data gradient of a 1x1 conv into its input `x` (a _Src): returns the gradient at the BatchNorm output
@@ -1162,6 +1234,16 @@ class Net:
         else:
             self.grad_hook(lo)
 
+    def _se_after_fused(self, B, HW, C, R):
+        """Gate-after-activation backward: the one-launch kernel or the three-launch sequence?  SE_AFTER_FUSED (None: by
+        shape, from the measurements in DESIGN.md; True / False: forced, for tests and tools/time_se_after.py).  The sequence
+        stays the path of the reference's own layouts (mobilenetv3_small), whose results therefore do not move."""
+        if self.arch.keys.scheme != 'timm' or C > 1024 or R > 1024:
+            return False
+        if SE_AFTER_FUSED is not None:
+            return bool(SE_AFTER_FUSED)
+        return _se_after_fused_by_shape(self.dt, B, HW, C, R)
+
     def _yfree_ok(self, x, M, K, Nn):
         """Expand layer on a finished bf16 input, wide enough that skipping the two extra passes over the M x N tensors
         pays for the three tiny extra launches (csrc/pwconv_yfree.hip)."""
@@ -1240,15 +1322,24 @@ class Net:
             wd, wp = self._wsel(self.wt[pwn])
             self._c('t3d_pwconv_dgrad', wd, N.ptr(dz), N.ptr(rec['y3']), bb3, wp, None, None, None,
                     N.ptr(dv), None, None, M2, HW2, C, blk.cout, st, nbytes=M2 * (C + blk.cout) * self.esz, bwd=rec['bn3'])
-            ps = self._buf(f'se_ps:{i}', (B, C, 2), torch.float32)
-            N.call('t3d_se_after_sums', dt, N.ptr(dv), N.ptr(s2.raw), se['pro2n'], N.ptr(ps), B, HW2, C, st)
             g = self._buf(f'se_g:{i}', (B, C), torch.float32)
             dq = self._buf(f'se_dq:{i}', (B, C), torch.float32)
             dp = self._buf(f'se_dp:{i}', (B, R), torch.float32)
+            if self._se_after_fused(B, HW2, C, R):
+                # the whole gate backward as ONE launch (csrc/se.hip: a workgroup per sample, the plane walked twice); it
+                # leaves dq / dp for the FC weight gradients of the second stream
+                dv2 = self._buf(f'dv2:{i}', (M2, C))
+                N.call('t3d_se_after_bwd', dt, N.ptr(dv), N.ptr(s2.raw), se['pro2n'], N.ptr(self.p[sen.se_w1]),
+                       N.ptr(self.p[sen.se_w2]), N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']), N.ptr(g), N.ptr(dq),
+                       N.ptr(dp), N.ptr(dv2), self._bst(bn2), B, HW2, C, R, st, nbytes=3 * M2 * C * self.esz)
+                self._se_wgrad(se, sen, dq, dp, B, C, R)
+                return self._block_bwd_tail(rec, dz, dv2, self._bn_bwd(bn2))
+            ps = self._buf(f'se_ps:{i}', (B, C, 2), torch.float32)
+            N.call('t3d_se_after_sums', dt, N.ptr(dv), N.ptr(s2.raw), se['pro2n'], N.ptr(ps), B, HW2, C, st)
             ones, zeros = self._const(C, 1.0), self._const(C, 0.0)
             self._pool_exact(False)
             N.call('t3d_se_bwd_data', N.ptr(ps), N.ptr(se['gap']), N.ptr(zeros), N.ptr(ones),
-                   N.ptr(self.p[sen + '.fc.0.weight']), N.ptr(self.p[sen + '.fc.2.weight']),
+                   N.ptr(self.p[sen.se_w1]), N.ptr(self.p[sen.se_w2]),
                    N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']), N.ptr(g), N.ptr(dq), N.ptr(dp), None,
                    B, C, R, se['HW'], st)            # (the before-activation sums are not needed here)
             self._se_wgrad(se, sen, dq, dp, B, C, R)
@@ -1273,7 +1364,7 @@ class Net:
             bn2 = s2.bn
             self._pool_exact(True)
             N.call('t3d_se_bwd_data', N.ptr(ps), N.ptr(se['gap']), N.ptr(bn2.scale), N.ptr(bn2.shift),
-                   N.ptr(self.p[sen + '.fc.0.weight']), N.ptr(self.p[sen + '.fc.2.weight']),
+                   N.ptr(self.p[sen.se_w1]), N.ptr(self.p[sen.se_w2]),
                    N.ptr(se['h']), N.ptr(se['q']), N.ptr(se['s']), N.ptr(g), N.ptr(dq), N.ptr(dp), self._bst(bn2),
                    B, C, R, se['HW'], st)
             self._se_wgrad(se, sen, dq, dp, B, C, R)
@@ -1283,6 +1374,16 @@ class Net:
             self._c('t3d_se_bwd_affine', N.ptr(se['s']), N.ptr(g), N.ptr(bn2.alpha), N.ptr(bn2.gammac), N.ptr(aps),
                     N.ptr(gps), B, C, st, bwd=bn2)
             bb2 = N.bnbwd(aps, bn2.bbeta, gps, True)
+        return self._block_bwd_tail(rec, dz, dv2, bb2)
+
+    def _block_bwd_tail(self, rec, dz, dv2, bb2):
+        """Depthwise conv and expansion of a block's backward: dv2 = gradient at the depthwise BatchNorm's output, bb2 its
+        backward affine."""
+        st, dt = N.stream(), self.dt
+        blk, i, x, s2 = rec['blk'], rec['idx'], rec['x'], rec['s2']
+        dwn = rec['names'][0]
+        B = x.B
+        M2 = s2.B * s2.H * s2.W
         M1 = B * x.H * x.W
         res = dz if blk.res else None
         if blk.expand:
@@ -1293,15 +1394,15 @@ class Net:
                     N.ptr(d1), self._bst(s1.bn), N.ptr(dwrep), B, x.H, x.W, blk.cexp, blk.k, blk.s, st,
                     nbytes=2 * (M1 + M2) * blk.cexp * self.esz, bwd=None if bb2.per_sample else s2.bn)
             bb1 = self._bn_bwd(s1.bn)
-            p = f'features.{i + 1}.conv'
+            expn = self.arch.keys.blocks[i].exp_w
             if self._yfree_ok(x, M1, blk.cin, blk.cexp):
-                return self._expand_bwd_yfree(d1, bb1, s1.bn, p + '.0.weight', x, res, M1, blk.cin, blk.cexp, i)
+                return self._expand_bwd_yfree(d1, bb1, s1.bn, expn, x, res, M1, blk.cin, blk.cexp, i)
             def exp_wgrad():
                 self._wgrad(dt, N.ptr(d1), N.ptr(s1.raw), bb1, N.ptr(x.t), x.pro,
-                            N.ptr(self.g[p + '.0.weight']), M1, x.H * x.W, blk.cin, blk.cexp,
+                            N.ptr(self.g[expn]), M1, x.H * x.W, blk.cin, blk.cexp,
                             nbytes=M1 * (blk.cin + blk.cexp) * self.esz, ro=s1.bn)
             exp_wgrad()
-            return self._pw_dgrad(d1, s1.raw, bb1, self.wt[p + '.0.weight'], x, res, M1, x.H * x.W, blk.cin,
+            return self._pw_dgrad(d1, s1.raw, bb1, self.wt[expn], x, res, M1, x.H * x.W, blk.cin,
                                   blk.cexp, f'dzin:{i}', s1.bn)
         # no-expand layout: the depthwise conv reads the block input directly
         dx = self._buf(f'dzin:{i}', (M1, blk.cexp))

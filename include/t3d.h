@@ -371,6 +371,18 @@ int t3d_se_after_sums(int dtype, const void* dv, const void* y, const t3d_prolog
 int t3d_se_after_apply(int dtype, const void* dv, const void* y, const t3d_prologue* pro, const float* s, const float* g,
                        void* du, double* stats, int B, int HW, int C, void* stream);
 
+/* The same backward as ONE launch (t3d_se_after_sums -> t3d_se_bwd_data with scale = 0, shift = 1, no stats ->
+ * t3d_se_after_apply).  The gate's input gradient g[b,:] depends only on sample b's own sums and on the two FC matrices,
+ * so a workgroup owns a whole sample: it walks the sample's plane once for sum_hw dv*a, runs the two small mat-vecs
+ * (w1 [R,C], w2 [C,R], fp32, read in their natural [I][O] orientation), then walks the plane a second time -- out of
+ * cache, not HBM -- for du and the BatchNorm sums.  h [B,R], q, s [B,C]: what the forward's t3d_se_fwd_fused left
+ * (the gate's input is mean_hw a, so g = dL/dm / HW).  Leaves g, dq [B,C], dp [B,R] for
+ * t3d_se_bwd_weights; du [B*HW,C] in the storage dtype; stats [2*C] fp64 += sum(du), sum(du*y), replica
+ * (workgroup % replicas) as set by t3d_set_reduction_replicas (may be NULL).  C % 8 == 0, C <= 1024, R <= 1024. */
+int t3d_se_after_bwd(int dtype, const void* dv, const void* y, const t3d_prologue* pro, const float* w1, const float* w2,
+                     const float* h, const float* q, const float* s, float* g, float* dq, float* dp, void* du,
+                     double* stats, int B, int HW, int C, int R, void* stream);
+
 /* Backward of the gate.  ps_stats [B,C,2] = per-sample sum_hw(dv), sum_hw(dv*y) from t3d_pwconv_dgrad
  * (dv: gradient at the gated tensor, y: raw depthwise output).  Produces g [B,C] (the pooled path's
  * per-pixel gradient, so that du = s*dv + g), accumulates the depthwise BatchNorm's backward sums
