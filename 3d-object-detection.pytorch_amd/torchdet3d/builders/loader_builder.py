@@ -5,6 +5,9 @@ int64 [B])` -- the reference's output contract (objectron_main.py:51-96 + utils/
 Any other root: the Objectron dataset (dataloaders/objectron.py) with the config's pipelines compiled by
 `build_augmentations` and applied on the GPU (`GpuAugmentLoader`, one `t3d_augment_crops_u8` launch per batch): batches
 `(imgs uint8 [B,oh,ow,3] NHWC on the device, gt_kp f32 [B,9,2], gt_cats int64 [B])`, normalised inside the stem.
+`cfg.data.cache = 'device'` (budget `cfg.data.cache_max_gb`, default 32): each of the three loaders decodes its dataset once,
+keeps the resized crops in device memory and serves every epoch from there (`t3d_augment_resized_u8`), the same batches
+bit for bit; under several ranks each rank caches the dataset it was given.
 
 One process per GPU (an unchanged scripts/main.py under `python -m torch.distributed.run`; `build_model`, called first by
 main.py:46, has joined the process group by the time main.py:63 builds the loaders): the reference's `nn.DataParallel`
@@ -65,6 +68,7 @@ def _build_objectron_loaders(config):
     tb, vb = config.data.train_batch_size or 8, config.data.val_batch_size or 8
     nw = config.data.num_workers or 0
     seed = int(getattr(getattr(config, 'utils', None), 'random_seeds', 0) or 0)
+    cache = dict(cache=config.data.cache or None, cache_max_gb=config.data.cache_max_gb or 32)
     world, rk = world_size(), rank()
     if tb % world:
         raise ValueError(f'data.train_batch_size = {tb} is the GLOBAL batch (scripts/main.py:60-61 scatters it over the '
@@ -73,11 +77,12 @@ def _build_objectron_loaders(config):
     # a shuffle that depends on (seed, epoch) only -- one rank is a DistributedSampler of one replica
     sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rk, shuffle=True, seed=seed,
                                                               drop_last=True)
-    train = GpuAugmentLoader(ds, train_tf, tb // world, sampler=sampler, num_workers=nw, drop_last=True, seed=seed, rank=rk)
+    train = GpuAugmentLoader(ds, train_tf, tb // world, sampler=sampler, num_workers=nw, drop_last=True, seed=seed, rank=rk,
+                             **cache)
     dv = Objectron(root, mode='val', transform=test_tf, category_list=cats)
     if world > 1:
         dv = torch.utils.data.Subset(dv, range(rk, len(dv), world))
-    val = GpuAugmentLoader(dv, test_tf, max(vb // world, 1), num_workers=nw, seed=seed, rank=rk)
+    val = GpuAugmentLoader(dv, test_tf, max(vb // world, 1), num_workers=nw, seed=seed, rank=rk, **cache)
     dt = Objectron(root, mode='test', transform=test_tf, category_list=cats)
-    test = GpuAugmentLoader(dt, test_tf, 1, num_workers=nw, seed=seed, rank=rk)
+    test = GpuAugmentLoader(dt, test_tf, 1, num_workers=nw, seed=seed, rank=rk, **cache)
     return train, val, test

@@ -10,6 +10,14 @@ Yields device tensors `(imgs uint8 [B, oh, ow, 3], keypoints float32 [B, 9, 2], 
 `Evaluator.val` and the step plan take them as they are.  The yielded tensors belong to the consumer (fresh allocations,
 recorded on the consumer's stream); only the pinned staging of the records rotates, each buffer guarded by the event of its
 last upload (the rule FrameCropper follows).
+
+`cache='device'` (`cfg.data.cache`): the pipeline resizes first, so resize(crop(frame)) is the same [oh, ow, 3] image in
+every epoch.  One pass over the dataset (`fill_cache`, run at the first `__iter__`) decodes every object once and stores that
+image -- `t3d_augment_crops_u8` with no flag set -- in an arena in device memory, slot i for dataset index i, with the
+keypoints, the crop size and the class of every index on the host.  After it an epoch walks `loader.batch_sampler` (the
+same batches, sharding and `set_epoch`), draws the same parameters with the same keys and launches
+`t3d_augment_resized_u8` over the arena: no worker, no decode, no upload of pixels, and batches equal to the uncached
+loader's bit for bit.  The arena must fit `cache_max_gb`; there is no partial cache.
 """
 import collections
 
@@ -17,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .objectron import collate_crops
+from .objectron import AUG_SAMPLE_DTYPE, collate_crops
 
 __all__ = ['GpuAugmentLoader']
 
@@ -47,8 +55,20 @@ class GpuAugmentLoader:
     NBUF = 3            # pinned record buffers in rotation
 
     def __init__(self, dataset, pipeline, batch_size, sampler=None, shuffle=False, num_workers=0, drop_last=False, seed=0,
-                 rank=0, prefetch=1):
+                 rank=0, prefetch=1, cache=None, cache_max_gb=32):
         self.pipeline, self.seed, self.rank, self.prefetch = pipeline, int(seed), int(rank), int(prefetch)
+        self.cache = cache or None
+        if self.cache is not None:
+            if self.cache != 'device':
+                raise ValueError(f"data.cache = {cache!r}: only 'device' (resized crops kept in GPU memory) or nothing is built")
+            oh, ow = pipeline.size
+            need, budget = len(dataset) * oh * ow * 3, int(float(cache_max_gb) * 2 ** 30)
+            if need > budget:
+                raise ValueError(f'data.cache: {len(dataset)} crops of {oh}x{ow}x3 need {need} bytes ({need / 2 ** 30:.3f} GiB), '
+                                 f'over the budget data.cache_max_gb = {cache_max_gb} ({budget} bytes); there is no partial cache')
+            self._arena = None                                 # uint8 [len(dataset) * oh * ow * 3] on the device (fill_cache)
+            self._c_kp = self._c_desc = self._c_cats = None    # per index: keypoints f64 [N,9,2], (0, h, w) i64 [N,3], class i64 [N]
+        self._num_workers = int(num_workers or 0)
         self.loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, sampler=sampler,
                                                   shuffle=shuffle if sampler is None else False,
                                                   num_workers=int(num_workers or 0), collate_fn=collate_crops,
@@ -78,15 +98,27 @@ class GpuAugmentLoader:
     def finish(self, host_batch, key_tail, prefetch=None):
         """One host batch -> device (imgs, keypoints, classes), enqueued on the copy stream (prefetch >= 1, with an event the
         caller hands to its consumer) or on the current stream (prefetch 0).  -> (imgs, kp, cats[, ready event])."""
-        prefetch = self.prefetch if prefetch is None else prefetch
         packed, desc, kp64, cats = host_batch
-        B = int(desc.shape[0])
+        dnp = desc.numpy()
+        return self._finish(packed, dnp, dnp, kp64.numpy(), cats.numpy(), key_tail, prefetch)
+
+    def finish_cached(self, indices, key_tail, prefetch=None):
+        """`finish` for a batch of dataset indices whose resized crops are in the arena."""
+        idx = np.asarray(indices, np.int64)
+        oh, ow = self.pipeline.size
+        where = np.stack([idx * (oh * ow * 3), np.full_like(idx, oh), np.full_like(idx, ow)], 1)     # (slot offset, oh, ow)
+        return self._finish(None, where, self._c_desc[idx], self._c_kp[idx], self._c_cats[idx], key_tail, prefetch)
+
+    def _finish(self, packed, where, dnp, kp64, cats, key_tail, prefetch):
+        """where [B, 3]: (offset, h, w) of the kernel's source images (the packed crops, or arena slots when `packed` is
+        None); dnp [B, 3]: the real crop sizes, which scale the keypoints."""
+        prefetch = self.prefetch if prefetch is None else prefetch
+        B = int(where.shape[0])
         oh, ow = self.pipeline.size
         epoch = int(getattr(self.loader.sampler, 'epoch', 0))
-        dnp = desc.numpy()
         prm = self.pipeline.draw(B, (self.seed, epoch, self.rank) + tuple(key_tail))
-        rec = self.pipeline.records(dnp, prm)
-        kp = self.pipeline.keypoints(kp64.numpy(), dnp, prm)
+        rec = self.pipeline.records(where, prm)
+        kp = self.pipeline.keypoints(kp64, dnp, prm)
         # one pinned upload for records | keypoints | classes (each part 8-byte aligned)
         nrec, nkp = B * rec.dtype.itemsize, B * 18 * 4
         nkp8 = (nkp + 7) // 8 * 8
@@ -95,7 +127,7 @@ class GpuAugmentLoader:
         host = slot[0]
         host[:nrec].numpy()[...] = rec.view(np.uint8)
         host[nrec:nrec + nkp].numpy()[...] = kp.reshape(-1).view(np.uint8)
-        host[nrec + nkp8:total].numpy()[...] = cats.numpy().astype(np.int64).view(np.uint8)
+        host[nrec + nkp8:total].numpy()[...] = cats.astype(np.int64).view(np.uint8)
         dev = torch.device('cuda', torch.cuda.current_device())
         stream = torch.cuda.current_stream(dev)
         if prefetch > 0:
@@ -107,9 +139,13 @@ class GpuAugmentLoader:
             meta.copy_(host[:total], non_blocking=True)
             slot[1] = torch.cuda.Event()
             slot[1].record(stream)
-            src = packed.to(dev, non_blocking=True)
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
-            N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
+            if packed is None:
+                N.call('t3d_augment_resized_u8', N.ptr(self._arena), self._arena.numel(), N.ptr(meta), N.ptr(imgs), B, oh, ow,
+                       N.stream())
+            else:
+                src = packed.to(dev, non_blocking=True)
+                N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
             kp_d = meta[nrec:nrec + nkp].view(torch.float32).view(B, 9, 2)
             cats_d = meta[nrec + nkp8:total].view(torch.int64)
         if prefetch > 0:
@@ -118,8 +154,50 @@ class GpuAugmentLoader:
             return imgs, kp_d, cats_d, ready
         return imgs, kp_d, cats_d
 
+    def fill_cache(self):
+        """The one decode pass: every dataset index, in order, through a DataLoader with the configured workers; its resized
+        crop goes into arena slot `index`.  The workers exit with the pass.  Idempotent."""
+        if self.cache is None:
+            raise RuntimeError("fill_cache() needs a loader built with cache='device'")
+        if self._arena is not None:
+            return
+        ds, (oh, ow) = self.dataset.host, self.pipeline.size
+        n, slot = len(ds), oh * ow * 3
+        dev = torch.device('cuda', torch.cuda.current_device())
+        arena = torch.empty(max(n * slot, 1), dtype=torch.uint8, device=dev)
+        c_kp, c_desc, c_cats = np.zeros((n, 9, 2), np.float64), np.zeros((n, 3), np.int64), np.zeros(n, np.int64)
+        it = iter(torch.utils.data.DataLoader(ds, batch_size=self.batch_size, shuffle=False, num_workers=self._num_workers,
+                                              collate_fn=collate_crops, pin_memory=True))
+        i0 = 0
+        for packed, desc, kp64, cats in it:
+            B = int(desc.shape[0])
+            rec = np.zeros(B, AUG_SAMPLE_DTYPE)          # flags 0: the resize alone
+            dnp = desc.numpy()
+            rec['offset'], rec['h'], rec['w'] = dnp[:, 0], dnp[:, 1], dnp[:, 2]
+            recd = torch.from_numpy(rec.view(np.uint8)).to(dev)
+            src = packed.to(dev, non_blocking=True)
+            out = arena[i0 * slot:(i0 + B) * slot]
+            if out.data_ptr() & 3:                             # the kernel stores dwords: an odd slot goes through a staging tensor
+                stage = torch.empty(B * slot, dtype=torch.uint8, device=dev)
+                N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(recd), N.ptr(stage), B, oh, ow, N.stream())
+                out.copy_(stage)
+            else:
+                N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(recd), N.ptr(out), B, oh, ow, N.stream())
+            c_kp[i0:i0 + B], c_cats[i0:i0 + B] = kp64.numpy(), cats.numpy()
+            c_desc[i0:i0 + B, 1:] = dnp[:, 1:]
+            i0 += B
+        del it                                                 # (the workers of a non-persistent DataLoader end with its iterator)
+        if i0 != n:
+            raise RuntimeError(f'fill_cache: the dataset yielded {i0} of {n} items')
+        torch.cuda.current_stream(dev).synchronize()           # epochs read the arena on the copy stream
+        self._arena, self._c_kp, self._c_desc, self._c_cats = arena, c_kp, c_desc, c_cats
+
     def __iter__(self):
-        it = iter(self.loader)
+        if self.cache is not None:
+            self.fill_cache()
+            it, finish = iter(self.loader.batch_sampler), self.finish_cached
+        else:
+            it, finish = iter(self.loader), self.finish
         pending, done, b = collections.deque(), False, 0
         while True:
             while not done and len(pending) <= self.prefetch:
@@ -128,7 +206,7 @@ class GpuAugmentLoader:
                 except StopIteration:
                     done = True
                     break
-                pending.append(self.finish(hb, (b,)))
+                pending.append(finish(hb, (b,)))
                 b += 1
             if not pending:
                 return

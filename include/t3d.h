@@ -254,6 +254,19 @@ typedef struct {
 int t3d_augment_crops_u8(const unsigned char* src, long long src_bytes, const void* samples, unsigned char* out, int B, int oh,
                          int ow, void* stream);
 
+/* The same augmentations over crops that are already resized (csrc/augment.hip): t3d_augment_crops_u8 with its resize
+ * stage replaced by a load.  Replaces the per-epoch `Objectron.__getitem__` + `A.Resize` of the reference
+ * (dataloaders/objectron_main.py:51-96: every epoch decodes, crops and resizes every object again): resize(crop(frame)) is
+ * the same image in every epoch, so the loader keeps it in device memory (dataloaders/gpu_loader.py, `cfg.data.cache`) and
+ * an epoch is a gather from that arena with flip, LUT, rotation and channel swap applied on the way out.
+ * arena: [oh, ow, 3] uint8 images, each at its record's byte `offset` (64-bit; any alignment); a record's h, w must equal
+ * oh, ow.  A record with another size, a negative offset or one that reaches past arena_bytes gives a zero image.
+ * samples: [B] t3d_aug_sample in DEVICE memory.  out [B, oh, ow, 3] uint8, 4-byte aligned.
+ * When the arena images are t3d_augment_crops_u8's output with no flag set, the result equals t3d_augment_crops_u8 on the
+ * original crops with the same flags, alpha, beta255 and m, bit for bit. */
+int t3d_augment_resized_u8(const unsigned char* arena, long long arena_bytes, const void* samples, unsigned char* out, int B,
+                           int oh, int ow, void* stream);
+
 /* Materialise a block output:  z = act(scale*y + shift) + residual   (residual may be NULL; scale NULL = identity).
  * Replaces the BatchNorm normalise pass + `x + self.conv(x)` (mobilenetv3.py:159,162-164). y,z,residual [M,C]. */
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
