@@ -445,6 +445,36 @@ int t3d_ssd_decode_nms(int dtype, int nlevels, const void* const* cls, const voi
                        int num_classes, float score_thr, float iou_thr, int max_per_class, float img_w, float img_h,
                        const float* stds, float* out, int* counts, void* stream);
 
+/* The demo's third stage: IOUTracker.process + get_tracked_objects of torchdet3d/utils/tracking_tools.py:127-290 (Track:
+ * :9-124; call site scripts/demo.py:56-78), one frame of S independent streams (cameras) per launch, one workgroup per
+ * stream; the whole tracker state lives in device memory and nothing is read back.  Per stream, in the reference's order:
+ * active tracks (end_time >= time - continue_time_thresh) in list order; cost[i][j] = 0.5 (1 - GIoU(det_i, last_box_j)) in
+ * fp64, stored as fp32; a minimum-cost assignment of the rectangular matrix (shortest augmenting paths with potentials, fp64
+ * on the fp32 costs; among equal optima which one is returned is unspecified); a pair survives when cost < match_threshold
+ * and IoU(last_box, det) > track_detection_iou_thresh; Track.add_detection (interpolation over a gap 1 < skip <=
+ * continue_time_thresh, box EMA int((1 - s) prev + s new) in fp64, the three-branch keypoint filter and the optional align_kp
+ * swap search); one new track per unassigned detection in detection order (id: FIFO of released ids, else last_global_id++);
+ * _clear_old_tracks with a stable compaction; then the get_tracked_objects selection at the advanced time.
+ * Deviations: only the LAST box / keypoints and the length of a track are kept (no histories, no archive: `cleared` counts
+ * the tracks that left through track_clear_thresh); keypoints are fp64 throughout; the table holds max_tracks tracks -- a
+ * detection that would open a track in a full table is not tracked and `dropped` is incremented.
+ *   state  [S][t3d_track_state_bytes(max_tracks)] bytes; ALL ZERO = a fresh tracker (time 0, no tracks, no ids handed out);
+ *   dets   [S][max_dets][4] int32 (left, top, right, bottom);  kps [S][max_dets][18] fp32;
+ *   counts [S] int32 valid detections per stream, clamped to [0, max_dets]; NULL: max_dets for every stream;
+ *   the eleven arguments of IOUTracker.__init__ (interpolate_time_thresh is stored but never read by the reference);
+ *   out_count [S]; out_boxes [S][max_tracks][4] int32; out_kp [S][max_tracks][18] fp64; out_ids [S][max_tracks] int32, -1 for a
+ *   track not longer than time_window (label 'ID -1'); rows past out_count are left as they were;
+ *   out_scalars [S][4] int32 = num_tracks, last_global_id, time, dropped.
+ * T3D_ERR_UNSUPPORTED when t3d_track_lds_bytes(max_dets, max_tracks) exceeds the 160 KiB of LDS a workgroup can have.
+ * t3d_track_state_bytes / t3d_track_lds_bytes RETURN byte counts (or T3D_ERR_ARG). */
+int t3d_track_state_bytes(int max_tracks);
+int t3d_track_lds_bytes(int max_dets, int max_tracks);
+int t3d_track_step(void* state, const int* dets, const float* kps, const int* counts, int S, int max_dets, int max_tracks,
+                   int time_window, int continue_time_thresh, int track_clear_thresh, double match_threshold,
+                   double track_detection_iou_thresh, int interpolate_time_thresh, double detection_filter_speed,
+                   double keypoints_filter_speed, double add_treshold, int no_updated_frames_treshold, int align_kp,
+                   int* out_count, int* out_boxes, double* out_kp, int* out_ids, int* out_scalars, void* stream);
+
 /* ---- ResNet-50 backbone (BASELINE config 4; the reference has no ResNet -- standard torchvision architecture, parity
  * against oracle/resnet.py, unpinned).  Dense k x k convolutions run as patch gather + the pointwise GEMM entry points
  * (t3d_pwconv_fwd / _dgrad / _wgrad with K = Kp); everything below is an HBM-bound gather / elementwise kernel. ---- */

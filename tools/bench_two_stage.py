@@ -1,8 +1,12 @@
 """Regression stage of the two-stage pipeline (BASELINE config 5's second stage): detections of a 1080x1920 uint8 frame ->
 crop + resize (t3d_crop_resize_u8) -> batched all-heads regression -> arg-max head, per frame.
-usage: python tools/bench_two_stage.py [--model mobilenetv2] [--dets 16] [--frames 200] [--dtype bf16]
+usage: python tools/bench_two_stage.py [--model mobilenetv2] [--dets 16] [--frames 200] [--dtype bf16] [--detector] [--track]
 Prints one JSON line: frames/s and crops/s with the frame resident in HBM, the same with the 6.2 MB H2D copy of every frame
-inside the timed region, and the oracle's host crop+resize loop (numpy, 1 core) for the same detections."""
+inside the timed region, and the oracle's host crop+resize loop (numpy, 1 core) for the same detections.
+--track adds the third stage (torchdet3d.utils.IOUTracker, t3d_track_step): the regression loop with the device tracker fed
+from Regressor.regress (one frame per launch, and --batch-frames cameras per launch), the same loop with what a host tracker
+needs instead (a D2H copy of rects and keypoints and a synchronisation per frame; the host tracker's own time not counted),
+and the HIP-event time of t3d_track_step alone for 1 / 8 / 32 streams."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, '3d-object-detection.pytorch_amd')]
@@ -18,6 +22,8 @@ ap.add_argument('--batch-frames', type=int, nargs='*', default=[8, 32], help='wi
                 'batched detector stage (Detector.get_detections_batch; BASELINE config 5 says "batched on 1 MI355X")')
 ap.add_argument('--detector', action='store_true', help='time the whole pipeline: SSD300-MobileNetV2 detector (models/ssd.py) '
                 'on the frame, then the regression stage on its detections (scripts/demo.py:48-90)')
+ap.add_argument('--track', action='store_true', help='add the tracking stage: device tracker fed from Regressor.regress, against '
+                'no tracking and against the per-frame D2H copy + sync a host tracker needs; t3d_track_step alone for 1 / 8 / 32 streams')
 args = ap.parse_args()
 
 from torchdet3d.builders import build_model
@@ -127,6 +133,84 @@ if args.detector:
                             'pipeline_ms_per_frame': round(tpb * 1e3, 3), 'pipeline_frames_per_s': round(1 / tpb, 1)}
     extra = {'pipeline_ms_per_frame': round(tp * 1e3, 3), 'pipeline_frames_per_s': round(1 / tp, 1), 'detections_regressed_per_frame': round(nd, 1),
              'detector_ms_per_frame': round(td * 1e3, 3), 'batched_frames_per_launch_chain': batched, 'detector': 'SSD300-MobileNetV2 (random weights), one frame per launch chain, host read-back of the detections'}
+if args.track:
+    from torchdet3d.utils import IOUTracker
+
+    def track_loop(frames, mode):
+        tr = IOUTracker(device='cuda', max_detections=n) if mode == 'device' else None
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(frames):
+            kp, labels = reg.regress(fd, rd)
+            if mode == 'device':
+                tr.process_device(rd, kp)
+            elif mode == 'host':
+                rd.cpu(), kp.cpu()              # what a host tracker needs every frame: both copies, each waits for the stream
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / frames
+
+    def track_loop_batched(fb, reps, track):
+        # fb cameras: the regression stage frame by frame, then ONE tracker launch for the fb streams
+        tr = IOUTracker(device='cuda', streams=fb, max_detections=n)
+        rb, kb = rd.unsqueeze(0).repeat(fb, 1, 1).contiguous(), torch.zeros(fb, n, 18, device='cuda')
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(reps):
+            for f in range(fb):
+                kp, labels = reg.regress(fd, rd)
+                if track:
+                    kb[f].copy_(kp.view(n, 18))
+            if track:
+                tr.process_batch_device(rb, kb)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / (reps * fb)
+
+    def step_alone(S, launches=200, dets=16):
+        # `dets` objects per stream, jittered by a few pixels from frame to frame: every detection continues its track
+        g = np.random.default_rng(1)
+        bx = g.integers(0, W - 400, (S, dets, 1)); by = g.integers(0, H - 400, (S, dets, 1))
+        base = np.concatenate([bx, by, bx + g.integers(90, 320, (S, dets, 1)), by + g.integers(90, 320, (S, dets, 1))], 2)
+        variants = [torch.from_numpy((base + g.integers(-3, 4, base.shape)).astype(np.int32)).cuda() for _ in range(8)]
+        kv = [torch.from_numpy((0.5 + g.normal(0, 0.01, (S, dets, 18))).astype(np.float32)).cuda() for _ in range(8)]
+        tr = IOUTracker(device='cuda', streams=S, max_detections=dets)
+        for i in range(16):
+            tr.process_batch_device(variants[i % 8], kv[i % 8])
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
+        torch.cuda.synchronize()
+        for i, (a, b) in enumerate(ev):
+            a.record()
+            tr.process_batch_device(variants[i % 8], kv[i % 8])
+            b.record()
+        torch.cuda.synchronize()
+        single = float(np.median([a.elapsed_time(b) for a, b in ev])) * 1e3
+        a, b = ev[0]
+        a.record()
+        for i in range(launches):
+            tr.process_batch_device(variants[i % 8], kv[i % 8])
+        b.record()
+        torch.cuda.synchronize()
+        nt = tr.num_tracks
+        return {'event_pair_median_us': round(single, 1), 'back_to_back_us': round(a.elapsed_time(b) / launches * 1e3, 1),
+                'tracks_per_stream': nt if isinstance(nt, int) else int(np.mean(nt))}
+
+    nf = args.frames
+    track_loop(20, 'device')
+    t_none, t_dev, t_host = track_loop(nf, None), track_loop(nf, 'device'), track_loop(nf, 'host')
+    tb = {}
+    for fb in args.batch_frames:
+        reps = max(3, nf // fb)
+        track_loop_batched(fb, 2, True)
+        a, b = track_loop_batched(fb, reps, False), track_loop_batched(fb, reps, True)
+        tb[str(fb)] = {'frames_per_s_no_tracking': round(1 / a, 1), 'frames_per_s_device_tracker': round(1 / b, 1)}
+    extra['tracking'] = {
+        'frames_per_s_no_tracking': round(1 / t_none, 1), 'frames_per_s_device_tracker': round(1 / t_dev, 1),
+        'frames_per_s_host_tracker_copies': round(1 / t_host, 1), 'ms_per_frame_no_tracking': round(t_none * 1e3, 3),
+        'ms_per_frame_device_tracker': round(t_dev * 1e3, 3), 'ms_per_frame_host_tracker_copies': round(t_host * 1e3, 3),
+        'cameras_per_tracker_launch': tb,
+        't3d_track_step_alone_16_dets': {str(S): step_alone(S) for S in (1, 8, 32)},
+        'what': 'regression loop + IOUTracker.process_device per frame; host_tracker_copies = D2H of rects and keypoints with '
+                'a synchronisation per frame (the host tracker itself not counted); step alone: HIP events around one launch '
+                '(includes the event records) and 200 launches back to back'}
 print(json.dumps({**extra, 'metric': f'two-stage regression stage, {n} detections per 1080x1920 frame, {args.model}', 'frames_per_s': round(1 / t_res, 1),
                   'crops_per_s': round(n / t_res, 1), 'ms_per_frame': round(t_res * 1e3, 3), 'frames_per_s_with_h2d': round(1 / t_up, 1),
                   'crop_resize_us': round(t_crop * 1e6, 1), 'dtype': args.dtype,
