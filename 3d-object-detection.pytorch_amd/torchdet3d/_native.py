@@ -78,6 +78,9 @@ SIGNATURES = {
     't3d_track_state_bytes': [_I],
     't3d_track_lds_bytes': [_I, _I],
     't3d_track_step': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _I, _D, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P],
+    't3d_ssd_select_rects': [_P, _P, _I, _I, _I, _I, _F, _F, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P],
+    't3d_head_select': [_P, _P, _I, _I, _I, _P, _P, _P],
+    't3d_track_kp_to_frame': [_P, _P, _P, _P, _I, _I, _P],
     't3d_im2col': [_I, _P, _PP, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     't3d_im2col_nchw': [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     't3d_col2im_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

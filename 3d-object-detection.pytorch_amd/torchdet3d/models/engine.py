@@ -649,12 +649,12 @@ class Net:
                 fpro = None
         # ---- heads (model_builder.py:137-144)
         ncls = self.num_classes
-        keep = self.persistent_outputs and not all_heads
+        keep = self.persistent_outputs
         # (persistent_outputs: the step plan's mode -- kp / logits live in engine buffers whose addresses do not change from
         # step to step; a caller of the plain API gets fresh tensors it may hold on to)
         logits = (self._buf('out:logits', (B, ncls), torch.float32) if keep else torch.empty(B, ncls, device=self.device)) if ncls > 1 else None
         if all_heads:
-            kp = torch.empty(9, B, 18, device=self.device)
+            kp = self._buf('out:kp_all', (9, B, 18), torch.float32) if keep else torch.empty(9, B, 18, device=self.device)
             N.call('t3d_head_fwd_all', N.ptr(f), fpro, N.ptr(self.wreg), N.ptr(self.breg),
                    N.ptr(self.p['cls_fc.1.weight']) if ncls > 1 else None,
                    N.ptr(self.p['cls_fc.1.bias']) if ncls > 1 else None, N.ptr(kp), N.ptr(logits), B, a.feat_c, ncls, st)

@@ -12,6 +12,7 @@ unpinned** (no source, no weights); the layers themselves are the product's own 
   heads      per level and branch: depthwise 3x3 (t3d_dwconv_fwd) -> BatchNorm + ReLU applied on load by the 1x1 conv
              with bias (t3d_pwconv_fwd); class branch A*(classes+1) channels (background last), box branch A*4
   post       t3d_ssd_decode_nms: decode + softmax + per-class NMS in one launch; the overall top-`max_per_img` on the host
+             (`detect`) or on the device (`detect_device` + t3d_ssd_select_rects: utils/pipeline.py)
 """
 import ctypes
 import math
@@ -89,6 +90,7 @@ class SSD300:
             self.p[k] = v.to(self.device)
         self._packed = None
         self._stds = (ctypes.c_float * 4)(*STDS)
+        self._persist, self._hbufs, self._dev = False, {}, {}
 
     def state_dict(self):
         sd = {'backbone.' + k: v for k, v in self.backbone.state_dict().items()
@@ -128,6 +130,16 @@ class SSD300:
             packed.append(lv)
         self._packed = packed
 
+    def _hbuf(self, key, shape):
+        """Head activation buffer: fresh per call, or -- inside `detect_device`, whose chain a plan may replay -- one
+        persistent tensor per (level, branch, shape)."""
+        if not self._persist:
+            return torch.empty(shape, device=self.device, dtype=self.dtype)
+        t = self._hbufs.get((key, shape))
+        if t is None:
+            t = self._hbufs[(key, shape)] = torch.empty(shape, device=self.device, dtype=self.dtype)
+        return t
+
     @torch.no_grad()
     def head_outputs(self, imgs):
         """imgs: uint8 NHWC [B,300,300,3] (normalised in the stem) or fp32 NCHW -> per level (cls [B*HW, n_cls], reg
@@ -141,9 +153,9 @@ class SSD300:
             lv, res = self._packed[l], []
             for br in ('cls_convs', 'reg_convs'):
                 h = lv[br]
-                y = torch.empty(B * H * W, C, device=self.device, dtype=self.dtype)
+                y = self._hbuf((l, br, 'y'), (B * H * W, C))
                 N.call('t3d_dwconv_fwd', self.dt, N.ptr(t), None, N.ptr(h['wdw']), N.ptr(y), None, None, B, H, W, C, 3, 1, st)
-                o = torch.empty(B * H * W, h['n'], device=self.device, dtype=self.dtype)
+                o = self._hbuf((l, br, 'o'), (B * H * W, h['n']))
                 N.call('t3d_pwconv_fwd', self.dt, N.ptr(y), h['pro'], N.ptr(h['w']), N.ptr(h['b']), N.ptr(o), None,
                        B * H * W, H * W, C, h['n'], st)
                 res.append(o)
@@ -151,27 +163,48 @@ class SSD300:
         return outs
 
     @torch.no_grad()
-    def detect(self, imgs):
-        outs = self.head_outputs(imgs)
-        B = imgs.shape[0]
+    def detect_device(self, imgs):
+        """The detector's launch chain with nothing read back: -> (out [B,nc,K,6] fp32: x1, y1, x2, y2 in input pixels, score,
+        label per class in NMS order; cnt [B,nc] int32 valid rows) on the device, in buffers that persist per batch size
+        (valid until the next call at that batch size; rows past cnt are stale -- the decode kernel writes every count and
+        the rows below it, so nothing needs clearing)."""
+        self._persist = True
+        try:
+            outs = self.head_outputs(imgs)
+        finally:
+            self._persist = False
+        B = int(imgs.shape[0])
         nl = len(outs)
-        P, I = ctypes.c_void_p * nl, ctypes.c_int * nl
-        cls, reg = P(*[o[0].data_ptr() for o in outs]), P(*[o[1].data_ptr() for o in outs])
-        hw, na = I(*[o[2] for o in outs]), I(*[len(WIDTHS[l]) for l in range(nl)])
-        cs, rs = I(*[o[0].shape[1] for o in outs]), I(*[o[1].shape[1] for o in outs])
         K = self.max_per_img
-        out = torch.zeros(B, self.nc, K, 6, device=self.device)
-        cnt = torch.zeros(B, self.nc, dtype=torch.int32, device=self.device)
-        N.call('t3d_ssd_decode_nms', self.dt, nl, cls, reg, hw, na, cs, rs, N.ptr(self.anchors), B, self.nc,
-               float(self.score_thr), float(self.iou_thr), K, float(INPUT_SIZE), float(INPUT_SIZE), self._stds,
-               N.ptr(out), N.ptr(cnt), N.stream())
+        d = self._dev.get(B)
+        if d is None:
+            d = self._dev[B] = dict(out=torch.zeros(B, self.nc, K, 6, device=self.device),
+                                    cnt=torch.zeros(B, self.nc, dtype=torch.int32, device=self.device))
+        P, I = ctypes.c_void_p * nl, ctypes.c_int * nl
+        # the per-level HOST arrays the entry point takes; handed over as addresses, which a recorded plan keeps as they are
+        host = (P(*[o[0].data_ptr() for o in outs]), P(*[o[1].data_ptr() for o in outs]), I(*[o[2] for o in outs]),
+                I(*[len(WIDTHS[l]) for l in range(nl)]), I(*[o[0].shape[1] for o in outs]), I(*[o[1].shape[1] for o in outs]))
+        d['host'] = host
+        if N.recorder is not None:
+            N.recorder.keep += [host, self._stds, outs, d['out'], d['cnt'], self.anchors]
+        N.call('t3d_ssd_decode_nms', self.dt, nl, *[ctypes.addressof(h) for h in host], N.ptr(self.anchors), B, self.nc,
+               float(self.score_thr), float(self.iou_thr), K, float(INPUT_SIZE), float(INPUT_SIZE),
+               ctypes.addressof(self._stds), N.ptr(d['out']), N.ptr(d['cnt']), N.stream())
+        return d['out'], d['cnt']
+
+    @staticmethod
+    def merge_classes(out, cnt, max_per_img, input_size=INPUT_SIZE):
+        """One image's `out [nc,K,6]` / `cnt [nc]` (numpy) -> [n,6] rows: mmdet multiclass_nms's best `max_per_img` over all
+        classes, by score (stable: class, then NMS order), boxes normalised to [0, 1]."""
+        nc = out.shape[0]
+        rows = np.concatenate([out[c, :cnt[c]] for c in range(nc)]) if cnt.sum() else np.zeros((0, 6), np.float32)
+        order = np.argsort(-rows[:, 4], kind='stable')[:max_per_img]
+        rows = rows[order]
+        rows[:, :4] /= input_size
+        return rows
+
+    @torch.no_grad()
+    def detect(self, imgs):
+        out, cnt = self.detect_device(imgs)
         out, cnt = out.cpu().numpy(), cnt.cpu().numpy()
-        res = []
-        for b in range(B):
-            rows = np.concatenate([out[b, c, :cnt[b, c]] for c in range(self.nc)]) if cnt[b].sum() else np.zeros((0, 6), np.float32)
-            # mmdet multiclass_nms: the best `max_per_img` over all classes, by score (stable: class, then NMS order)
-            order = np.argsort(-rows[:, 4], kind='stable')[:self.max_per_img]
-            rows = rows[order]
-            rows[:, :4] /= INPUT_SIZE
-            res.append(rows)
-        return res
+        return [self.merge_classes(out[b], cnt[b], self.max_per_img) for b in range(out.shape[0])]

@@ -5,3 +5,4 @@ from .geometry import lift_2d, project_3d_points, convert_2d_to_ndc, convert_cam
     get_default_camera_matrix
 from .ie_wrappers import Regressor, Detector
 from .tracking_tools import IOUTracker, TrackedObj
+from .pipeline import FramePipeline

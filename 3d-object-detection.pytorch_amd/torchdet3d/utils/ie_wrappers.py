@@ -66,6 +66,42 @@ class Regressor:
         kp = kp_all[labels, torch.arange(n, device=self.device)]
         return kp, labels
 
+    @torch.no_grad()
+    def regress_device(self, frames, crop_rects, n, out=None):
+        """The regression stage inside a device-resident frame chain (utils/pipeline.py): `frames` [S,H,W,3] (or [H,W,3])
+        uint8 stacked as one frame of S*H rows, `crop_rects` [n,4] int32 rectangles into that stack (`t3d_ssd_select_rects`)
+        -> (kp [n,9,2] fp32 of the arg-max class's head, labels [n] int32), views into the wrapper's buffers, valid until the
+        next call (or `out` = (kp [n,18] fp32, labels [n] int32) device tensors of the caller).  One crop launch, one
+        all-heads forward at batch n, `t3d_head_select`; only library launches, in buffers whose addresses do not move, so a
+        recorded plan can replay the chain."""
+        n = int(n)
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.shape[-1] == 3
+        assert crop_rects.is_cuda and crop_rects.dtype == torch.int32 and crop_rects.is_contiguous() and crop_rects.numel() >= 4 * n
+        rows = int(frames.shape[0]) * int(frames.shape[1]) if frames.dim() == 4 else int(frames.shape[0])
+        if n > self._crops.shape[0]:
+            self._crops = torch.empty(n, self.h, self.w, 3, dtype=torch.uint8, device=self.device)
+        crops = self._crops[:n]
+        st = N.stream()
+        N.call('t3d_crop_resize_u8', N.ptr(frames), N.ptr(crop_rects), N.ptr(crops), n, rows, int(frames.shape[-2]), self.h, self.w, st)
+        net = self.model.net_eval
+        net.persistent_outputs = True
+        try:
+            kp_all, logits = net.forward(crops, None, train=False, all_heads=True)       # [9,n,9,2], [n,C] or None
+        finally:
+            net.persistent_outputs = False
+        if out is None:
+            sel = self.__dict__.setdefault('_sel', {})
+            if n not in sel:
+                sel[n] = (torch.zeros(n, 18, device=self.device), torch.zeros(n, dtype=torch.int32, device=self.device))
+            out = sel[n]
+        kp, labels = out
+        assert kp.dtype == torch.float32 and kp.numel() == 18 * n and labels.dtype == torch.int32 and labels.numel() == n
+        C = int(logits.shape[1]) if logits is not None else 1
+        if N.recorder is not None:
+            N.recorder.keep += [crops, kp_all, logits, kp, labels]
+        N.call('t3d_head_select', N.ptr(kp_all), N.ptr(logits), n, int(kp_all.shape[0]), C, N.ptr(labels), N.ptr(kp), st)
+        return kp.view(n, 9, 2), labels
+
     # ---- the reference's host API ------------------------------------------------------------------------------------
     def get_detections(self, frame, detections):
         """Returns [(kp ndarray [1,9,2], label)] for all detections on `frame` (ndarray [H,W,3] uint8 or a device tensor),

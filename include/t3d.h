@@ -475,6 +475,44 @@ int t3d_track_step(void* state, const int* dets, const float* kps, const int* co
                    double keypoints_filter_speed, double add_treshold, int no_updated_frames_treshold, int align_kp,
                    int* out_count, int* out_boxes, double* out_kp, int* out_ids, int* out_scalars, void* stream);
 
+/* The joints of the live pipeline (scripts/demo.py:56-78: detector -> regressor -> tracker -> keypoints in frame pixels) on
+ * the device (csrc/pipeline.hip), so that a frame is one chain of launches with no host round trip.
+ *
+ * t3d_ssd_select_rects: t3d_ssd_decode_nms's out [F][num_classes][max_per_class][6] / counts [F][num_classes] -> per frame
+ * the list the host code builds today (models/ssd.py: SSD300.detect's merge, utils/ie_wrappers.py:94-120:
+ * Detector._decode_detections), cut to max_dets rows; one workgroup per frame, every step in the host's own precision:
+ *   the rows class-major, the first counts[f][c] of each class; stable sort by descending score, the first max_per_img;
+ *   x / input_size in fp32; a row stays when score > conf (fp32: a score equal to the rounded threshold is dropped);
+ *   left = (int)((x1 > 0 ? x1 : 0) * (float)frame_w), an fp32 product truncated towards zero; top / right / bottom alike;
+ *   unless (expand_w, expand_h) == (1, 1): w = right - left, dw = w * (expand_w - 1) / 2 in fp64,
+ *   left = max((int)(left - dw), 0), right = (int)(right + dw); top / bottom alike with expand_h;
+ *   stable sort by descending top; the first max_dets.
+ *   rects [F][max_dets][4] int32 (left, top, right, bottom: the unclipped frame-pixel boxes);
+ *   crop_rects [F*max_dets][4] int32: the same boxes clamped to [0, frame_w] x [0, frame_h] (numpy slice semantics) with
+ *   f * frame_h added to the rows -- rectangles into the F frames stacked as ONE frame of F * frame_h rows, which is how
+ *   t3d_crop_resize_u8 crops all of them in one launch;
+ *   scores [F][max_dets] fp32; det_labels [F][max_dets] int32; counts [F] int32 rows written (<= max_dets);
+ *   overflow [F] int32: rows that passed the threshold and fell to the cap max_dets.
+ * Rows at or past counts[f] are ZERO in every output (t3d_crop_resize_u8 makes black crops of them).
+ * T3D_ERR_UNSUPPORTED when num_classes * max_per_class > 4096 (the candidates of a frame are sorted in LDS). */
+int t3d_ssd_select_rects(const float* out, const int* cnt, int F, int num_classes, int max_per_class, int max_per_img,
+                         float input_size, float conf, int frame_h, int frame_w, double expand_w, double expand_h,
+                         int max_dets, int* rects, int* crop_rects, float* scores, int* det_labels, int* counts, int* overflow,
+                         void* stream);
+
+/* The head of the arg-max class (utils/ie_wrappers.py:135-139): kp_all [num_heads][n][18] fp32 (t3d_head_fwd_all), logits
+ * [n][num_classes] fp32 -> labels [n] int32 = the lowest index among the row's maxima (0 when num_classes <= 1 or logits is
+ * NULL), kp [n][18] = kp_all[labels[i]][i].  One workgroup per row.  num_classes <= num_heads. */
+int t3d_head_select(const float* kp_all, const float* logits, int n, int num_heads, int num_classes, int* labels, float* kp,
+                    void* stream);
+
+/* Regressor.transform_kp (utils/ie_wrappers.py:144-152) on every tracked object (scripts/demo.py:78), one workgroup per
+ * stream, from t3d_track_step's outputs: kp_frame [S][max_tracks][18] fp64, x = round(kp_x * (right - left)) then
+ * round(x + left), y alike with top / bottom -- two fp64 roundings, as numpy does them.  Rows past out_count[s] are left
+ * as they were. */
+int t3d_track_kp_to_frame(const int* out_count, const int* out_boxes, const double* out_kp, double* kp_frame, int S,
+                          int max_tracks, void* stream);
+
 /* ---- ResNet-50 backbone (BASELINE config 4; the reference has no ResNet -- standard torchvision architecture, parity
  * against oracle/resnet.py, unpinned).  Dense k x k convolutions run as patch gather + the pointwise GEMM entry points
  * (t3d_pwconv_fwd / _dgrad / _wgrad with K = Kp); everything below is an HBM-bound gather / elementwise kernel. ---- */

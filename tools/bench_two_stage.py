@@ -1,12 +1,18 @@
 """Regression stage of the two-stage pipeline (BASELINE config 5's second stage): detections of a 1080x1920 uint8 frame ->
 crop + resize (t3d_crop_resize_u8) -> batched all-heads regression -> arg-max head, per frame.
-usage: python tools/bench_two_stage.py [--model mobilenetv2] [--dets 16] [--frames 200] [--dtype bf16] [--detector] [--track]
+usage: python tools/bench_two_stage.py [--model mobilenetv2] [--dets 16] [--frames 200] [--dtype bf16] [--detector] [--track] [--pipeline]
 Prints one JSON line: frames/s and crops/s with the frame resident in HBM, the same with the 6.2 MB H2D copy of every frame
 inside the timed region, and the oracle's host crop+resize loop (numpy, 1 core) for the same detections.
 --track adds the third stage (torchdet3d.utils.IOUTracker, t3d_track_step): the regression loop with the device tracker fed
 from Regressor.regress (one frame per launch, and --batch-frames cameras per launch), the same loop with what a host tracker
 needs instead (a D2H copy of rects and keypoints and a synchronisation per frame; the host tracker's own time not counted),
-and the HIP-event time of t3d_track_step alone for 1 / 8 / 32 streams."""
+and the HIP-event time of t3d_track_step alone for 1 / 8 / 32 streams.
+--pipeline times the joined three-stage loop instead (torchdet3d.utils.FramePipeline) and prints / appends one JSON line per
+(cameras, cap) to profiles/pipeline_two_stage_bench.jsonl: S in {1, 8} cameras of 1080x1920 frames resident in HBM, cap D = 16
+with the confidence set so that about 16 rows pass and D = 64 at the same confidence (what padding costs), three forms
+alternated in one process, three repetitions each: (a) the host-joined chain per camera (Detector.get_detections ->
+Regressor.get_detections -> IOUTracker.process -> get_tracked_objects -> transform_kp), (b) the pipeline launch by launch,
+(c) the pipeline replayed from its recorded plan."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, '3d-object-detection.pytorch_amd')]
@@ -24,6 +30,8 @@ ap.add_argument('--detector', action='store_true', help='time the whole pipeline
                 'on the frame, then the regression stage on its detections (scripts/demo.py:48-90)')
 ap.add_argument('--track', action='store_true', help='add the tracking stage: device tracker fed from Regressor.regress, against '
                 'no tracking and against the per-frame D2H copy + sync a host tracker needs; t3d_track_step alone for 1 / 8 / 32 streams')
+ap.add_argument('--pipeline', action='store_true', help='time the joined detector -> regressor -> tracker -> frame-pixel keypoints '
+                'loop: host-joined chain against FramePipeline launch by launch and replayed; S in {1, 8}, D in {16, 64}')
 args = ap.parse_args()
 
 from torchdet3d.builders import build_model
@@ -34,6 +42,104 @@ cfg = AttrDict(dict(model=dict(name=args.model, num_classes=9, pretrained=False,
 model = build_model(cfg, export_mode=True).to('cuda')
 model.eval()
 H, W, n = 1080, 1920, args.dets
+
+
+def bench_pipeline():
+    from torchdet3d.models.ssd import SSD300
+    from torchdet3d.utils import Detector, FramePipeline, IOUTracker
+    det = Detector(SSD300('cuda', torch.bfloat16 if args.dtype == 'bf16' else torch.float32), conf=0.0)
+    gd = torch.Generator().manual_seed(0)
+    sd = det.model.state_dict()
+    for k in sd:                      # trained-looking BatchNorm buffers and biases: the scores must tell the anchors apart
+        if k.startswith('bbox_head') and k.endswith('running_mean'):
+            sd[k] = torch.randn(sd[k].shape, generator=gd) * 0.1
+        elif k.startswith('bbox_head') and k.endswith('running_var'):
+            sd[k] = torch.rand(sd[k].shape, generator=gd) + 0.5
+        elif k.startswith('bbox_head.cls_convs') and k.endswith('.3.bias'):
+            sd[k] = torch.randn(sd[k].shape, generator=gd) * 2.0
+        elif k.startswith('bbox_head.reg_convs') and k.endswith('.3.bias'):
+            sd[k] = torch.randn(sd[k].shape, generator=gd) * 0.5
+    det.model.load_state_dict(sd)
+    rng = np.random.default_rng(0)
+    # blocks of 16 x 16 pixels: structure that survives the resize to 300 x 300 (white noise averages to one grey for every anchor)
+    coarse = rng.integers(0, 256, (8, -(-H // 16), W // 16, 3), dtype=np.uint8)
+    cams = torch.from_numpy(np.ascontiguousarray(coarse.repeat(16, 1).repeat(16, 2)[:, :H])).cuda()
+    img, _ = det._enqueue(cams[0])
+    sc = np.sort(det.model.detect(img)[0][:, 4])[::-1]
+    cuts = [i for i in range(1, len(sc)) if sc[i - 1] > sc[i]]                      # (equal scores cannot be split)
+    cut = min(cuts, key=lambda i: abs(i - 16))
+    det.confidence = float((np.float64(sc[cut - 1]) + np.float64(sc[cut])) / 2)     # `cut` rows of camera 0 pass: 16, or the nearest
+    frames_per_figure = max(args.frames, 200)
+    out_path = os.path.join(ROOT, 'profiles', 'pipeline_two_stage_bench.jsonl')
+    lines = []
+    for S in (1, 8):
+        fr = cams[:S].contiguous()
+        iters = -(-frames_per_figure // S)
+        for D in (16, 64):
+            reg = Regressor(model, (224, 224), max_detections=S * D)
+            solo = [IOUTracker(device='cuda', max_detections=D) for _ in range(S)]
+            os.environ['T3D_STEP_PLAN'] = '0'
+            direct = FramePipeline(det, reg, IOUTracker(device='cuda', streams=S, max_detections=D))
+            os.environ.pop('T3D_STEP_PLAN')
+            replayed = FramePipeline(det, reg, IOUTracker(device='cuda', streams=S, max_detections=D))
+            passed = []
+
+            def host_chain(k):
+                for _ in range(k):
+                    for s in range(S):
+                        dets = det.get_detections(fr[s])[:D]
+                        outs = reg.get_detections(fr[s], dets)
+                        solo[s].process(fr[s], dets, [o[0].reshape(-1) for o in outs])
+                        objs = solo[s].get_tracked_objects()
+                        [Regressor.transform_kp(np.array(o.kp).reshape(9, 2), o.rect[:4]) for o in objs]
+                        passed.append(len(dets))
+
+            def device_chain(pipe):
+                def go(k):
+                    for _ in range(k):
+                        pipe.process_device(fr)
+                return go
+
+            def host_lists(pipe):
+                def go(k):
+                    for _ in range(k):
+                        pipe.process(fr[0])
+                return go
+            forms = {'a_host_joined': host_chain, 'b_launch_by_launch': device_chain(direct), 'c_replayed': device_chain(replayed)}
+            if S == 1:      # the demo's four host lists per frame: one read-back and one synchronisation each
+                forms.update(b_launch_by_launch_host_lists=host_lists(direct), c_replayed_host_lists=host_lists(replayed))
+            for go in forms.values():                                  # warm-up of every form at this shape (records the plan)
+                go(6)
+            torch.cuda.synchronize()
+            assert replayed.replays > 0 and direct.replays == 0
+            ms = {k: [] for k in forms}
+            for _ in range(3):
+                for k, go in forms.items():
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    go(iters)
+                    torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t) / (iters * S) * 1e3)
+            res = replayed.process_device(fr)
+            line = {'metric': 'joined detector -> regressor -> tracker -> frame-pixel keypoints, 1080x1920 frames in HBM', 'cameras': S,
+                    'cap_D': D, 'model': args.model, 'dtype': args.dtype, 'camera_frames_per_figure': iters * S, 'conf': round(det.confidence, 6),
+                    'rows_passing_per_camera': res['counts'].tolist(), 'overflow_per_camera': res['overflow'].tolist(),
+                    'host_chain_detections_per_camera_frame': round(float(np.mean(passed)), 2),
+                    'ms_per_camera_frame': {k: {'median': round(float(np.median(v)), 4), 'min': round(min(v), 4), 'max': round(max(v), 4),
+                                                'runs': [round(x, 4) for x in v]} for k, v in ms.items()},
+                    'camera_frames_per_s': {k: round(1e3 / float(np.median(v)), 1) for k, v in ms.items()}}
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+            del direct, replayed
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, 'w') as f:
+        f.write(''.join(json.dumps(l) + '\n' for l in lines))
+
+
+if args.pipeline:
+    from torchdet3d.utils import Regressor as _R      # noqa: F401
+    bench_pipeline()
+    sys.exit(0)
 rng = np.random.default_rng(0)
 frame = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
 x0 = rng.integers(0, W - 400, n); y0 = rng.integers(0, H - 400, n)
