@@ -81,6 +81,8 @@ SIGNATURES = {
     't3d_ssd_select_rects': [_P, _P, _I, _I, _I, _I, _F, _F, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P],
     't3d_head_select': [_P, _P, _I, _I, _I, _P, _P, _P],
     't3d_track_kp_to_frame': [_P, _P, _P, _P, _I, _I, _P],
+    't3d_objectron_pairs': [_P] * 7 + [_I, _I, _I, _D, _D, _P, _P, _P],
+    't3d_objectron_hitmiss': [_P] * 8 + [_I] * 5 + [_P] * 6,
     't3d_im2col': [_I, _P, _PP, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     't3d_im2col_nchw': [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     't3d_col2im_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -513,6 +513,40 @@ int t3d_head_select(const float* kp_all, const float* logits, int n, int num_hea
 int t3d_track_kp_to_frame(const int* out_count, const int* out_boxes, const double* out_kp, double* kp_frame, int S,
                           int max_tracks, void* stream);
 
+/* The Objectron evaluation protocol of the reference's final report (scripts/objectron_eval.py:116-175 around
+ * objectron.dataset.eval.Evaluator) on the device (csrc/objectron_eval.hip), F frames per launch pair, fp64 throughout.
+ * The dependency is absent from the reference: DESIGN.md section 7 states the protocol, parity with
+ * the upstream package is unpinned.
+ *
+ * t3d_objectron_pairs: one workgroup per (frame, prediction slot): match, lift, ground-plane scale, the six metrics.
+ *   pred_kp [F][P][9][2] fp64 keypoints, multiplied by (sx, sy) on load: (1, 1) for keypoints normalised to the frame,
+ *   (1 / W, 1 / H) for frame pixels (FramePipeline's kp_frame [S][T][18]);  pred_count [F] int32, clamped to [0, P];
+ *   gt_kp2d [F][G][9][2] fp64 normalised; gt_kp3d [F][G][9][3] fp64, camera frame, metric scale; gt_visibility [F][G] fp64;
+ *   gt_count [F] int32, clamped to [0, G]; planes [F][6] fp64 = centre, normal.
+ *   A prediction matches i* = argmin_i ||pred[1:9] - kp2d_i[1:9]||_F (first minimum), or nothing when visibility[i*] < 0.1.
+ *   metrics [F][P][6] fp64 = pixel, azimuth, polar, iou, add, adds -- unmatched: 0.1, 30, 20, 0, 1, 1; matched: mean corner
+ *   pixel distance; lift_2d(pred, portrait) with the default NDC camera, scaled by mean(centre.normal / d[0:4]), d = the
+ *   ascending corner dot products with the normal; absolute azimuth (wrapped at 180) / polar difference in degrees of the
+ *   viewpoints (T = Oh Vh^T (Vh Vh^T)^-1 with O the unit box scaled by V's edge lengths; (x, y, z) = T[0:3][3]); the IoU of
+ *   t3d_box_iou3d; mean corner distance and mean nearest-corner distance over the 9 vertices.  A non-finite intermediate is
+ *   carried into the metric (no trap).  matched [F][P] int32 = i* or -1.  Slots at or past pred_count[f] are left untouched.
+ *
+ * t3d_objectron_hitmiss: one workgroup per frame, writes row base + f of the evaluator's record (capacity rows):
+ *   valid [row] = 1 when the frame has an instance with visibility > 0.1, centre keypoint strictly inside (0, 1)^2 and
+ *   kp3d[0].z < 0, else 0 and the rest of the row is zero; num_instances [row] = the clamped gt_count[f];
+ *   thresholds [6][21] fp64 in the metric order above (computed by the HOST: numpy.linspace, never on the device);
+ *   hit / miss [row][6][21] int32 over the frame's predictions in slot order: hit when iou >= thr, or value <= thr for the
+ *   other five (a nan misses everywhere);  sums [row][5] fp64 = error_2d, iou_3d, azimuth, polar over the matched
+ *   predictions (finite values only), matched count.  Deterministic: plain stores, no atomics.
+ * Both only enqueue on `stream`; T3D_ERR_ARG for a NULL pointer, F, P or G <= 0, base < 0 or base + F > capacity. */
+int t3d_objectron_pairs(const double* pred_kp, const int* pred_count, const double* gt_kp2d, const double* gt_kp3d,
+                        const double* gt_visibility, const int* gt_count, const double* planes, int F, int P, int G, double sx,
+                        double sy, double* metrics, int* matched, void* stream);
+int t3d_objectron_hitmiss(const double* metrics, const int* matched, const int* pred_count, const double* gt_kp2d,
+                          const double* gt_kp3d, const double* gt_visibility, const int* gt_count, const double* thresholds,
+                          int F, int P, int G, int base, int capacity, int* valid, int* num_instances, int* hit, int* miss,
+                          double* sums, void* stream);
+
 /* ---- ResNet-50 backbone (BASELINE config 4; the reference has no ResNet -- standard torchvision architecture, parity
  * against oracle/resnet.py, unpinned).  Dense k x k convolutions run as patch gather + the pointwise GEMM entry points
  * (t3d_pwconv_fwd / _dgrad / _wgrad with K = Kp); everything below is an HBM-bound gather / elementwise kernel. ---- */
