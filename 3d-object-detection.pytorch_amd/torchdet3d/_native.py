@@ -38,6 +38,12 @@ class BnFold(ctypes.Structure):          # t3d_bn_fold (include/t3d.h); lives in
                 ('o3', _P), ('o4', _P), ('mean', _P), ('invstd', _P)]
 
 
+class DrawStyleC(ctypes.Structure):      # t3d_draw_style (include/t3d.h); utils/draw.py: DrawStyle packs to it
+    _fields_ = [('rect_th', _I), ('edge_th', _I), ('kp_radius', _I), ('font_scale', _I), ('flags', _I),
+                ('colors', ctypes.c_ubyte * 3 * 8)]
+
+
+DRAW_IDS = 1                    # include/t3d.h: T3D_DRAW_IDS
 _PP = ctypes.POINTER(Prologue)
 _BP = ctypes.POINTER(BnBwd)
 _LP = ctypes.POINTER(LossCfg)
@@ -81,6 +87,8 @@ SIGNATURES = {
     't3d_ssd_select_rects': [_P, _P, _I, _I, _I, _I, _F, _F, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P],
     't3d_head_select': [_P, _P, _I, _I, _I, _P, _P, _P],
     't3d_track_kp_to_frame': [_P, _P, _P, _P, _I, _I, _P],
+    't3d_draw_overlays_u8': [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.POINTER(DrawStyleC), _P],
+    't3d_draw_glyphs': [_P, _I],
     't3d_objectron_pairs': [_P] * 7 + [_I, _I, _I, _D, _D, _P, _P, _P],
     't3d_objectron_hitmiss': [_P] * 8 + [_I] * 5 + [_P] * 6,
     't3d_im2col': [_I, _P, _PP, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

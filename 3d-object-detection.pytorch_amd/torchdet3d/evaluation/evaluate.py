@@ -1,15 +1,16 @@
 """Validation loop (torchdet3d/evaluation/evaluate.py:73-149): eval-mode forward with the ground-truth class
 selecting the regression head (:92), per-class meters weighted by the whole batch size (:96-100, as the reference
 does), TensorBoard scalars `Val/{ADD,SADD,ACC,IOU}`, a plain-text table in place of PrettyTable; and `visual_test`
-(:31-72): per-sample forward + metrics on a few test samples (the jpg drawing needs cv2 + objectron.graphics, which
-this image does not have: the predicted / true keypoints are saved as .npy next to where the jpgs would go)."""
+(:31-72): per-sample forward + metrics on a few test samples; the predicted / true keypoints are saved as .npy and drawn
+into `tested_image_{idx}_predicted.jpg` / `_true.jpg` by the device draw stage (utils/draw.py: this project's own raster
+rules -- cv2 and objectron.graphics are absent -- so the look is unpinned against the reference's jpgs)."""
 import os.path as osp
 
 import numpy as np
 import torch
 
 from ..parallel import all_reduce_sums, is_main, world_size
-from ..utils import AverageMeter, put_on_device, mkdir_if_missing, OBJECTRON_CLASSES
+from ..utils import AverageMeter, put_on_device, mkdir_if_missing, draw_kp, OBJECTRON_CLASSES
 from .metrics import compute_accuracy, compute_average_distance, compute_metrics_per_cls, enqueue_metrics_per_cls
 
 
@@ -26,7 +27,9 @@ class Evaluator:
     def visual_test(self):
         """evaluate.py:31-72 over the TEST loader's dataset (the reference rebuilds `Objectron(root, mode='test')`,
         which is the dataset behind `test_loader`, loader_builder.py:31-34): forward one sample at a time with the
-        ground-truth class selecting the head, print ADD / SADD / accuracy, store the keypoints."""
+        ground-truth class selecting the head, print ADD / SADD / accuracy, store the keypoints and the annotated jpgs: a
+        test-mode item is drawn on its full frame (keypoints in frame pixels), any other item with a uint8 HWC image on that
+        crop; float images (already normalised for the network) are not drawn."""
         ds = getattr(self.test_loader, 'dataset', None)
         if not is_main():          # one process per GPU: rank 0 runs the few visual samples and writes their files
             return []
@@ -40,12 +43,12 @@ class Evaluator:
             assert isinstance(self.samples, list)
             indexes = self.samples
         self.model.eval()
-        results = []
+        results, told = [], False
         for idx in indexes:
             item = ds[int(idx)]
-            crop_cords = None
+            crop_cords, frame = None, None
             if len(item) == 5:                     # test-mode Objectron item (objectron_main.py:93-94)
-                _, img, gt_kp, gt_cat, crop_cords = item
+                frame, img, gt_kp, gt_cat, crop_cords = item
             else:
                 img, gt_kp, gt_cat = item
             img, gt_kp = put_on_device([torch.as_tensor(img), torch.as_tensor(gt_kp)], self.device)
@@ -63,6 +66,16 @@ class Evaluator:
             label = OBJECTRON_CLASSES[int(torch.argmax(pred_cat, dim=1))] if pred_cat.dtype.is_floating_point else None
             np.save(osp.join(self.path_to_save_imgs, f'tested_image_{idx}_predicted.npy'), pk)
             np.save(osp.join(self.path_to_save_imgs, f'tested_image_{idx}_true.npy'), gk)
+            # evaluate.py:62-70: the same two pictures, drawn by the device stage
+            canvas = np.asarray(frame) if frame is not None else img
+            if canvas.dtype in (np.uint8, torch.uint8) and len(canvas.shape) == 3 and canvas.shape[2] == 3:
+                gt_label = int(cat[0]) if 0 <= int(cat[0]) < len(OBJECTRON_CLASSES) else None
+                for kps, lab, tag in ((pk, label, 'predicted'), (gk, gt_label, 'true')):
+                    draw_kp(canvas, kps, osp.join(self.path_to_save_imgs, f'tested_image_{idx}_{tag}.jpg'),
+                            normalized=crop_cords is None, label=lab, device=self.device)
+            elif not told:
+                told = True
+                print('visual_test: the images are not uint8 [H, W, 3] (normalised for the network), no jpgs are drawn')
             results.append(dict(idx=int(idx), ADD=ADD, SADD=SADD, accuracy=accuracy, label=label))
         return results
 

@@ -5,4 +5,5 @@ from .geometry import lift_2d, project_3d_points, convert_2d_to_ndc, convert_cam
     get_default_camera_matrix
 from .ie_wrappers import Regressor, Detector
 from .tracking_tools import IOUTracker, TrackedObj
+from .draw import DrawStyle, draw_overlays, draw_kp
 from .pipeline import FramePipeline

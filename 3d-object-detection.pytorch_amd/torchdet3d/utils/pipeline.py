@@ -21,6 +21,7 @@ import torch
 
 from .. import _native as N
 from ..trainer.step_plan import WARM_STEPS
+from .draw import DrawStyle
 from .tracking_tools import TrackedObj
 
 __all__ = ['FramePipeline']
@@ -32,10 +33,13 @@ def _resolved(dev):
 
 
 class FramePipeline:
-    """`FramePipeline(detector, regressor, tracker)`: S = `tracker.streams` cameras, D = `tracker.max_detections`.
-    `replays` counts the frames that ran as one `t3d_plan_run` (T3D_STEP_PLAN=0 keeps the launch-by-launch form)."""
+    """`FramePipeline(detector, regressor, tracker, draw=None)`: S = `tracker.streams` cameras, D = `tracker.max_detections`.
+    `replays` counts the frames that ran as one `t3d_plan_run` (T3D_STEP_PLAN=0 keeps the launch-by-launch form).
+    `draw`: a `DrawStyle` -- the chain then ends with the demo's `draw_detections` (scripts/demo.py:79-81) as one more launch:
+    the tracked objects' rectangles, boxes, keypoints and class names are drawn on `frames` IN PLACE (utils/draw.py; the look
+    is unpinned against the reference's).  None (default): the frames are left as they are."""
 
-    def __init__(self, detector, regressor, tracker):
+    def __init__(self, detector, regressor, tracker, draw=None):
         if not torch.cuda.is_available():
             raise RuntimeError('the frame pipeline runs on the GPU (no CPU fallback)')
         self.device = _resolved(detector.device)
@@ -48,6 +52,10 @@ class FramePipeline:
         self.replay = os.environ.get('T3D_STEP_PLAN', '1') != '0'      # read here: 0 keeps this pipeline launch by launch
         self.slots = (ctypes.c_ulonglong * N.NSLOTS)()
         self._block = None
+        if draw is not None and not isinstance(draw, DrawStyle):
+            raise ValueError('draw must be a DrawStyle or None')
+        self.draw = draw
+        self._style = draw.pack() if draw is not None else None       # (copied into the launch, and into a recorded plan)
 
     # ---- buffers ---------------------------------------------------------------------------------------------------------
     def _allocate(self):
@@ -94,6 +102,11 @@ class FramePipeline:
         tr.process_batch_device(o['rects'], o['kp'], o['counts'])
         t = tr._o
         N.call('t3d_track_kp_to_frame', N.ptr(t['count']), N.ptr(t['boxes']), N.ptr(t['kp']), N.ptr(o['kp_frame']), S, self.T, st)
+        if self._style is not None:
+            # scripts/demo.py:79: the tracked objects zipped in index order with the regressor's outputs (their labels).  The
+            # launch reads kp_frame, the chain's last product, so it is behind every reader of the frames it draws on
+            N.call('t3d_draw_overlays_u8', N.ptr(frames), S, H, W, N.ptr(t['count']), N.ptr(t['boxes']), N.ptr(o['kp_frame']),
+                   N.ptr(t['ids']), N.ptr(o['labels']), N.ptr(o['counts']), D, self.T, self._style, st)
 
     def _results(self):
         o, t = self._o, self.tracker._o
@@ -107,7 +120,7 @@ class FramePipeline:
         (the detector's rows, zeros past counts), labels [S,D] int32 and kp [S,D,18] (crop-normalised, of the arg-max head),
         everything `IOUTracker.tracked_device()` returns under its own names (count, boxes, ids, scalars) except the tracked
         keypoints [S,T,18] float64, which are `track_kp` here (`kp` is the regressor's), and kp_frame [S,T,18] float64 (the
-        tracked keypoints in frame pixels).  Never synchronises."""
+        tracked keypoints in frame pixels).  With `draw` set, `frames` carries the overlays afterwards.  Never synchronises."""
         S = self.S
         if frames.dim() == 3 and S == 1:
             frames = frames.unsqueeze(0)
@@ -115,13 +128,16 @@ class FramePipeline:
             raise ValueError(f'frames must be a uint8 device tensor [{S}, H, W, 3]')
         if _resolved(frames.device) != self.device:
             raise ValueError(f'frames on {frames.device}, the pipeline on {self.device}')
+        if self._style is not None and not frames.is_contiguous():
+            raise ValueError('frames must be contiguous: the overlays are drawn on them in place')
         frames = frames.contiguous()
         H, W = int(frames.shape[1]), int(frames.shape[2])
         if self._block is None:
             self._allocate()
         # (the detector's threshold / expand ratio and the tracker's settings are literal words of a recorded plan: a change
         # of any of them is a new plan too)
-        key = (S, H, W, frames.dtype, N.stream(), float(self.detector.confidence), tuple(self.detector.expand_ratio), self._tracker_settings())
+        key = (S, H, W, frames.dtype, N.stream(), float(self.detector.confidence), tuple(self.detector.expand_ratio), self._tracker_settings(),
+               bytes(self._style) if self._style is not None else None)
         if key != self.key:
             self.drop()
             self._shape_buffers(S, H, W)

@@ -513,6 +513,42 @@ int t3d_head_select(const float* kp_all, const float* logits, int n, int num_hea
 int t3d_track_kp_to_frame(const int* out_count, const int* out_boxes, const double* out_kp, double* kp_frame, int S,
                           int max_tracks, void* stream);
 
+/* The last stage of the live loop (scripts/demo.py:26-46 draw_detections + utils/utils.py:247-270 draw_kp): rectangles, the
+ * 12 box edges, 9 keypoint discs and a label plate with text, drawn IN PLACE on frames [S][H][W][3] uint8 by one launch for
+ * all cameras (csrc/draw.hip).  OpenCV and objectron.graphics are absent, so the raster rules are this project's own, all in
+ * integers (DESIGN.md section 7 states them; tests/draw_ref.py restates them in numpy and the kernel is bit-equal to that);
+ * the LOOK (colours, thickness, font) is unpinned against the reference's output.
+ *   count [S] int32 or NULL (= T objects per camera), clamped to [0, T]; objects are drawn in index order, a later object
+ *   over an earlier one; within an object: rectangle (boxes [S][T][4] int32 left, top, right, bottom, or NULL: none), the
+ *   12 edges (4 along x, 4 along y, 4 along z, a colour per axis), discs of keypoints 0..8, label plate, label text.
+ *   kp [S][T][18] fp64 in frame pixels (FramePipeline's kp_frame); a point is rint(x), rint(y) (half to even) and is skipped,
+ *   with every edge that uses it, unless both are finite and |.| <= 8191.
+ *   ids [S][T] int32 or NULL; ids < 0 (the tracker's "not longer than time_window"): the rectangle takes the "off" colour,
+ *   edges and discs are not drawn, plate and text are.
+ *   labels: object t of camera s has class labels[s * label_stride + t] when t < label_count[s] (clamped to
+ *   [0, label_stride]; NULL label_count: every entry), else none; the text is the Objectron class name of a label in 0..8,
+ *   followed by " <id>" when flags has T3D_DRAW_IDS and id >= 0; an empty text has no plate.  NULL labels: no class text.
+ * style is a HOST struct, copied into the launch: rect_th, edge_th in 1..16, kp_radius in 0..32, font_scale in 1..8 (the
+ * font is a 5 x 7 bitmap, a font pixel is font_scale x font_scale, the advance 6 * font_scale), colours in the frame's own
+ * channel order: rectangle, rectangle "off", edges along x / y / z, keypoint, plate, text.
+ * 1 <= H, W <= 8192, 1 <= T <= 1024, S <= 65535; S == 0 returns T3D_OK without a launch; T3D_ERR_ARG for NULL frames / kp /
+ * style, sizes or style fields out of range, label_stride < 1 (or < T with a NULL label_count) when labels is given.
+ * A workgroup owns a 64 x 16 pixel tile and leaves without touching global memory when no primitive's bounding box meets
+ * it; a thread stores only bytes of its own four pixels (aligned dwords when frames is 4-byte aligned and W % 4 == 0, bytes
+ * otherwise); no global atomics: the result does not depend on scheduling.
+ * t3d_draw_glyphs copies the font out: 38 glyphs (a-z, 0-9, '_', ' ') of 7 row bytes, column c of a row at bit 4 - c; any
+ * other character is drawn as a filled cell.  Copies min(bytes, 266) bytes and RETURNS 266 (T3D_ERR_ARG: bytes < 0, or a
+ * NULL out with bytes > 0). */
+#define T3D_DRAW_IDS 1
+typedef struct {
+  int rect_th, edge_th, kp_radius, font_scale, flags;
+  unsigned char colors[8][3];
+} t3d_draw_style;
+int t3d_draw_overlays_u8(unsigned char* frames, int S, int H, int W, const int* count, const int* boxes, const double* kp,
+                         const int* ids, const int* labels, const int* label_count, int label_stride, int T,
+                         const t3d_draw_style* style, void* stream);
+int t3d_draw_glyphs(unsigned char* out, int bytes);
+
 /* The Objectron evaluation protocol of the reference's final report (scripts/objectron_eval.py:116-175 around
  * objectron.dataset.eval.Evaluator) on the device (csrc/objectron_eval.hip), F frames per launch pair, fp64 throughout.
  * The dependency is absent from the reference: DESIGN.md section 7 states the protocol, parity with

@@ -1,6 +1,6 @@
 """Regression stage of the two-stage pipeline (BASELINE config 5's second stage): detections of a 1080x1920 uint8 frame ->
 crop + resize (t3d_crop_resize_u8) -> batched all-heads regression -> arg-max head, per frame.
-usage: python tools/bench_two_stage.py [--model mobilenetv2] [--dets 16] [--frames 200] [--dtype bf16] [--detector] [--track] [--pipeline]
+usage: python tools/bench_two_stage.py [--model mobilenetv2] [--dets 16] [--frames 200] [--dtype bf16] [--detector] [--track] [--pipeline [--draw]]
 Prints one JSON line: frames/s and crops/s with the frame resident in HBM, the same with the 6.2 MB H2D copy of every frame
 inside the timed region, and the oracle's host crop+resize loop (numpy, 1 core) for the same detections.
 --track adds the third stage (torchdet3d.utils.IOUTracker, t3d_track_step): the regression loop with the device tracker fed
@@ -12,7 +12,10 @@ and the HIP-event time of t3d_track_step alone for 1 / 8 / 32 streams.
 with the confidence set so that about 16 rows pass and D = 64 at the same confidence (what padding costs), three forms
 alternated in one process, three repetitions each: (a) the host-joined chain per camera (Detector.get_detections ->
 Regressor.get_detections -> IOUTracker.process -> get_tracked_objects -> transform_kp), (b) the pipeline launch by launch,
-(c) the pipeline replayed from its recorded plan."""
+(c) the pipeline replayed from its recorded plan.
+--draw (with --pipeline) adds (d) / (e): forms (b) / (c) with the draw stage as the chain's last launch (FramePipeline(draw=DrawStyle()),
+on a copy of the frames of their own: the overlays stay on it from frame to frame), at D = 16 only, and writes
+profiles/pipeline_draw_bench.jsonl instead."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, '3d-object-detection.pytorch_amd')]
@@ -32,6 +35,8 @@ ap.add_argument('--track', action='store_true', help='add the tracking stage: de
                 'no tracking and against the per-frame D2H copy + sync a host tracker needs; t3d_track_step alone for 1 / 8 / 32 streams')
 ap.add_argument('--pipeline', action='store_true', help='time the joined detector -> regressor -> tracker -> frame-pixel keypoints '
                 'loop: host-joined chain against FramePipeline launch by launch and replayed; S in {1, 8}, D in {16, 64}')
+ap.add_argument('--draw', action='store_true', help='with --pipeline: also time the pipeline with the draw stage (boxes, keypoints and '
+                'labels drawn on the frames in place) launch by launch and replayed')
 args = ap.parse_args()
 
 from torchdet3d.builders import build_model
@@ -70,12 +75,12 @@ def bench_pipeline():
     cut = min(cuts, key=lambda i: abs(i - 16))
     det.confidence = float((np.float64(sc[cut - 1]) + np.float64(sc[cut])) / 2)     # `cut` rows of camera 0 pass: 16, or the nearest
     frames_per_figure = max(args.frames, 200)
-    out_path = os.path.join(ROOT, 'profiles', 'pipeline_two_stage_bench.jsonl')
+    out_path = os.path.join(ROOT, 'profiles', 'pipeline_draw_bench.jsonl' if args.draw else 'pipeline_two_stage_bench.jsonl')
     lines = []
     for S in (1, 8):
         fr = cams[:S].contiguous()
         iters = -(-frames_per_figure // S)
-        for D in (16, 64):
+        for D in ((16,) if args.draw else (16, 64)):
             reg = Regressor(model, (224, 224), max_detections=S * D)
             solo = [IOUTracker(device='cuda', max_detections=D) for _ in range(S)]
             os.environ['T3D_STEP_PLAN'] = '0'
@@ -106,12 +111,27 @@ def bench_pipeline():
                         pipe.process(fr[0])
                 return go
             forms = {'a_host_joined': host_chain, 'b_launch_by_launch': device_chain(direct), 'c_replayed': device_chain(replayed)}
+            if args.draw:
+                from torchdet3d.utils import DrawStyle
+                fr_draw = fr.clone()
+                os.environ['T3D_STEP_PLAN'] = '0'
+                direct_draw = FramePipeline(det, reg, IOUTracker(device='cuda', streams=S, max_detections=D), draw=DrawStyle())
+                os.environ.pop('T3D_STEP_PLAN')
+                replayed_draw = FramePipeline(det, reg, IOUTracker(device='cuda', streams=S, max_detections=D), draw=DrawStyle())
+
+                def draw_chain(pipe):
+                    def go(k):
+                        for _ in range(k):
+                            pipe.process_device(fr_draw)
+                    return go
+                forms.update(d_launch_by_launch_draw=draw_chain(direct_draw), e_replayed_draw=draw_chain(replayed_draw))
             if S == 1:      # the demo's four host lists per frame: one read-back and one synchronisation each
                 forms.update(b_launch_by_launch_host_lists=host_lists(direct), c_replayed_host_lists=host_lists(replayed))
             for go in forms.values():                                  # warm-up of every form at this shape (records the plan)
                 go(6)
             torch.cuda.synchronize()
             assert replayed.replays > 0 and direct.replays == 0
+            assert not args.draw or (replayed_draw.replays > 0 and direct_draw.replays == 0)
             ms = {k: [] for k in forms}
             for _ in range(3):
                 for k, go in forms.items():
