@@ -19,7 +19,7 @@
 // t3d_dw_flush -- bit-reproducible; fp32 atomics into replicas when the caller provides no slots).
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -45,237 +45,9 @@ struct Dw3BArgs {
 
 template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
 
-template <typename T, int CH, int PF>
-__global__ __launch_bounds__(256) void dw3_bwd_s1_kernel(const Dw3BArgs a) {
-  extern __shared__ float lred[];  // end of kernel: [11][C] fp64 accumulators: dw taps 0..8, sum(dx), sum(dx*x)
-  using RV = rawvec<T, CH>;
-  const int CG = a.C / CH;
-  int cg, ox_fixed = 0, q0, qstride;
-  bool on;
-  if (!a.slab) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    on = j < a.W * CG;
-    cg = on ? j % CG : 0;
-    ox_fixed = on ? j / CG : 0;
-    q0 = blockIdx.y;
-    qstride = gridDim.y;
-  } else {
-    cg = blockIdx.y * 64 + (threadIdx.x & 63);
-    on = cg < CG;
-    if (!on) cg = 0;
-    q0 = blockIdx.x * 4 + (threadIdx.x >> 6);
-    qstride = gridDim.x * 4;
-  }
-  const int c0 = cg * CH;
-  const bool affine = a.scale != nullptr || a.act != T3D_ACT_NONE;
-  const bool need_x = affine || a.stats != nullptr || a.dw != nullptr;
-
-  float wt[9][CH], sc[CH], sh[CH], al[CH], be[CH], ga[CH], psum[CH], psq[CH], wacc[9][CH];
-  {
-    float wb[CH * 9];
-    const float4* wp = reinterpret_cast<const float4*>(a.w + (size_t)c0 * 9);
-#pragma unroll
-    for (int i = 0; i < CH * 9 / 4; ++i) {
-      const float4 q = wp[i];
-      wb[4 * i] = q.x; wb[4 * i + 1] = q.y; wb[4 * i + 2] = q.z; wb[4 * i + 3] = q.w;
-    }
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      sc[i] = a.scale ? a.scale[c0 + i] : 1.f;
-      sh[i] = a.scale ? a.shift[c0 + i] : 0.f;
-      be[i] = a.beta[c0 + i];
-      al[i] = a.per_sample ? 0.f : a.alpha[c0 + i];
-      ga[i] = a.per_sample ? 0.f : a.gamma[c0 + i];
-      psum[i] = psq[i] = 0.f;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        wt[t][i] = wb[i * 9 + t];
-        wacc[t][i] = 0.f;
-      }
-    }
-  }
-
-  for (int q = q0; q < a.nitems && on; q += qstride) {
-    int ox, rest;
-    if (!a.slab) { ox = ox_fixed; rest = q; } else { ox = q % a.W; rest = q / a.W; }
-    const int chunk = rest % a.nchunks, b = rest / a.nchunks;
-    const size_t img = (size_t)b * a.H * a.W * a.C + c0;
-    const T* __restrict__ zg = reinterpret_cast<const T*>(a.dz) + img;
-    const T* __restrict__ yg = reinterpret_cast<const T*>(a.y) + img;
-    const T* __restrict__ xg = reinterpret_cast<const T*>(a.x) + img;
-    const T* __restrict__ rg = a.res ? reinterpret_cast<const T*>(a.res) + img : nullptr;
-    T* __restrict__ dxg = reinterpret_cast<T*>(a.dx) + img;
-    if (a.per_sample) {
-#pragma unroll
-      for (int i = 0; i < CH; ++i) {
-        al[i] = a.alpha[(size_t)b * a.C + c0 + i];
-        ga[i] = a.gamma[(size_t)b * a.C + c0 + i];
-      }
-    }
-    const int r0 = chunk * a.rows_per_chunk, r1 = min(a.H, r0 + a.rows_per_chunk);  // rows owned by this item
-    const int ix0 = ox - 1;
-    const bool cok[3] = {ix0 >= 0, true, ix0 + 2 < a.W};
-    // dgrad stencil: dy column c (= x-1+c) reaches dx column x through tap kx = 2-c
-    float wd[9][CH];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < CH; ++i) wd[ky * 3 + c][i] = cok[c] ? wt[ky * 3 + (2 - c)][i] : 0.f;
-    int coff[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) coff[c] = min(max(ix0 + c, 0), a.W - 1) * a.C;
-
-    RV rz[PF][3], ry[PF][3], rx[PF][3];
-    auto fetch = [&](int r, int slot) {
-      const size_t ro = (size_t)min(max(r, 0), a.H - 1) * a.W * a.C;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        rz[slot][c] = *reinterpret_cast<const RV*>(zg + ro + coff[c]);
-        ry[slot][c] = *reinterpret_cast<const RV*>(yg + ro + coff[c]);
-        if (need_x) rx[slot][c] = *reinterpret_cast<const RV*>(xg + ro + coff[c]);
-      }
-    };
-    const int rf = r0 - 1, rl = r1;  // rows walked (inclusive): one halo row on each side
-#pragma unroll
-    for (int u = 0; u < PF; ++u) fetch(rf + u, u);
-
-    static_assert(PF == 3, "accumulator roles come from the unroll index");
-    float acc[3][CH];          // dx rows r-1, r, r+1 = acc[u%3], acc[(u+1)%3], acc[(u+2)%3]
-    float a_prev[3][CH];       // activations of row r-1 (three columns)
-    float dyc_prev[CH];        // centre gradient of row r-1 (zero when that row is not owned / outside)
-    float xc_prev[CH];         // raw centre input of row r-1 (for act' and the sums)
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      acc[0][i] = acc[1][i] = acc[2][i] = 0.f;
-      a_prev[0][i] = a_prev[1][i] = a_prev[2][i] = 0.f;
-      dyc_prev[i] = xc_prev[i] = 0.f;
-    }
-    for (int base = rf; base <= rl; base += PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int r = base + u;
-        if (r <= rl) {
-          const bool rok = r >= 0 && r < a.H;
-          float dy[3][CH], av[3][CH], xc[CH];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-              // rounded to the storage precision, as the tiled kernel stages it (bit-compatible sums are not required,
-              // but the two kernels should agree to rounding)
-              dy[c][i] = rok ? fmaf(al[i], (float)rz[u][c][i], fmaf(be[i], (float)ry[u][c][i], ga[i])) : 0.f;
-              av[c][i] = need_x ? (float)rx[u][c][i] : 0.f;
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < CH; ++i) xc[i] = av[1][i];
-          if (affine) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) act_affine_vec<CH>(av[c], sc, sh, a.act);
-          }
-#pragma unroll
-          for (int i = 0; i < CH; ++i) {   // zero padding of the activated input
-            av[0][i] = (rok && cok[0]) ? av[0][i] : 0.f;
-            av[1][i] = rok ? av[1][i] : 0.f;
-            av[2][i] = (rok && cok[2]) ? av[2][i] : 0.f;
-          }
-          fetch(r + PF, u);
-          float* accA = acc[u % 3];
-          float* accB = acc[(u + 1) % 3];
-          float* accC = acc[(u + 2) % 3];
-          // ---- data gradient: dy row r -> dx rows r-1 (ky=0), r (ky=1), r+1 (ky=2)
-          if (rok) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-              for (int i = 0; i < CH; ++i) {
-                accA[i] = fmaf(dy[c][i], wd[c][i], accA[i]);
-                accB[i] = fmaf(dy[c][i], wd[3 + c][i], accB[i]);
-                accC[i] = fmaf(dy[c][i], wd[6 + c][i], accC[i]);
-              }
-          }
-          // ---- weight gradient: owned output rows only (the halo rows belong to the neighbouring chunk)
-          if (a.dw) {
-            const bool own = r >= r0 && r < r1;
-            float dyc[CH];
-#pragma unroll
-            for (int i = 0; i < CH; ++i) dyc[i] = own ? dy[1][i] : 0.f;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-              for (int i = 0; i < CH; ++i) {
-                wacc[kx][i] = fmaf(dyc[i], a_prev[kx][i], wacc[kx][i]);          // ky = 0: a row r-1
-                wacc[3 + kx][i] = fmaf(dyc[i], av[kx][i], wacc[3 + kx][i]);      // ky = 1: a row r
-                wacc[6 + kx][i] = fmaf(dyc_prev[i], av[kx][i], wacc[6 + kx][i]);  // ky = 2: dy row r-1, a row r
-              }
-#pragma unroll
-            for (int i = 0; i < CH; ++i) dyc_prev[i] = dyc[i];
-          }
-          // ---- dx row r-1 is complete
-          const int iy = r - 1;
-          if (iy >= r0 && iy < r1) {
-            float g[CH];
-#pragma unroll
-            for (int i = 0; i < CH; ++i) g[i] = accA[i];
-            if (affine) act_grad_affine_vec<CH>(g, xc_prev, sc, sh, a.act);
-            const size_t off = ((size_t)iy * a.W + ox) * a.C;
-            if (rg) {
-              const RV rr = *reinterpret_cast<const RV*>(rg + off);
-#pragma unroll
-              for (int i = 0; i < CH; ++i) g[i] += (float)rr[i];
-            }
-            RV o;
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-              o[i] = (T)g[i];
-              const float v = (float)o[i];
-              psum[i] += v;
-              psq[i] = fmaf(v, xc_prev[i], psq[i]);
-            }
-            *reinterpret_cast<RV*>(dxg + off) = o;
-          }
-#pragma unroll
-          for (int i = 0; i < CH; ++i) {
-            accA[i] = 0.f;
-            xc_prev[i] = xc[i];
-            a_prev[0][i] = av[0][i];
-            a_prev[1][i] = av[1][i];
-            a_prev[2][i] = av[2][i];
-          }
-        }
-      }
-    }
-  }  // item loop
-
-  // ---- block-level reduction of the weight gradient and the BatchNorm-backward sums
-  const int nred = (a.dw ? 9 : 0) + (a.stats ? 2 : 0);
-  if (nred && !a.noflush) {
-    double* lacc = reinterpret_cast<double*>(lred);       // [9 + 2][a.C] fp64 accumulators (common.h: t3d_dw_flush)
-    for (int i = threadIdx.x; i < 11 * a.C; i += 256) lacc[i] = 0.0;
-    __syncthreads();
-    if (on) {
-#pragma unroll
-      for (int i = 0; i < CH; ++i) {
-        if (a.dw) {
-#pragma unroll
-          for (int t = 0; t < 9; ++t) atomicAdd(lacc + t * a.C + c0 + i, (double)wacc[t][i]);
-        }
-        if (a.stats) {
-          atomicAdd(lacc + 9 * a.C + c0 + i, (double)psum[i]);
-          atomicAdd(lacc + 10 * a.C + c0 + i, (double)psq[i]);
-        }
-      }
-    }
-    __syncthreads();
-    t3d_dw_flush<9, 256>(lacc, a.C, 0, a.C, a.dw, a.stats, a.nrep, a.rstride, a.dw_slots, (int)(blockIdx.y * gridDim.x + blockIdx.x), a.dw_used);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// Two columns per thread + packed fp32 math (the production stride-1 backward).  The one-column kernel above needs
-// ~310 VALU instructions per output vector and is VALU-bound at ~1.2 TB/s; here four column loads of dz / y / x feed
+// Two columns per thread + packed fp32 math (the stride-1 backward).  One column per thread (the header's skeleton, retired) needed
+// ~310 VALU instructions per output vector and was VALU-bound at ~1.2 TB/s; here four column loads of dz / y / x feed
 // two outputs (dy and the activations are formed twice per element instead of three times), every multiply-add is a
 // v_pk_fma_f32, and the 9 x CH stencil weights are read from LDS per use (saves 36 registers for the two
 // accumulator sets).  Padding: 0/1 masks per out-of-image column, wave-uniform row skips.
@@ -743,8 +515,7 @@ template <typename T, int CH>
 int launch_s1c(Dw3BArgs& a, hipStream_t st) {
   constexpr int PF = 3;
   const int CG = a.C / CH;
-  const bool two_col = true;
-  const int Wcols = two_col ? (a.W + 1) / 2 : a.W;
+  const int Wcols = (a.W + 1) / 2;     // column pairs
   const long long per_row_chunk = (long long)a.B * Wcols * CG;
   int nchunks = (int)((256LL * 64 * 24 + per_row_chunk - 1) / per_row_chunk);
   int max_chunks = a.H / 8;
@@ -756,7 +527,7 @@ int launch_s1c(Dw3BArgs& a, hipStream_t st) {
   dim3 grid;
   // tools/sweep_dwb.sh: the 4-channel variant needs AGPR spill space (1 wave/SIMD) and is best with one block per CU;
   // the 2-channel variant fits 2 waves/SIMD and is best with two (every extra block is one more flush)
-  const int target_blocks = CH == 2 && two_col ? 512 : 256;
+  const int target_blocks = CH == 2 ? 512 : 256;
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   const int nth = 256;   // 512-thread blocks measured 4-5x slower (register budget)
@@ -782,22 +553,14 @@ int launch_s1c(Dw3BArgs& a, hipStream_t st) {
     if (gx < 1) gx = 1;
     grid = dim3(gx, ns);
   }
-  // 32-bit buffer offsets, and the dropped-lane sentinel 0x80000000 has to stay out of range.  This return sits in front
-  // of t3d_take_fold below: a refused launch must leave a pending finalize request for the tiled fallback to honour.
-  if (two_col && (size_t)a.B * a.H * a.W * a.C * sizeof(T) >= (1ull << 31)) return T3D_ERR_UNSUPPORTED;
   {   // depthwise weight gradient: one slot per workgroup when the caller provides enough of them (t3d_set_dw_slots)
-    const int needed = (two_col && a.slab) ? (int)grid.x : (int)(grid.x * grid.y);
+    const int needed = a.slab ? (int)grid.x : (int)(grid.x * grid.y);
     a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
     a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
   }
-  const size_t lds = (size_t)22 * ((two_col && a.slab) ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64 reduction scratch (before it: [9][Cb] weights, [3][Cb] derived coefficients)
-  // a pending BatchNorm-backward finalize of this launch's gradient coefficients is derived in the two-column kernel
-  if (two_col && !a.per_sample) {
-    a.fold = t3d_take_fold(a.alpha);
-  } else {
-    if (const int rc = t3d_fold_fallback(a.alpha, st)) return rc;
-    a.fold = nullptr;
-  }
+  const size_t lds = (size_t)22 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64 reduction scratch (before it: [9][Cb] weights, [3][Cb] derived coefficients)
+  // a pending BatchNorm-backward finalize of this launch's shared gradient coefficients is derived in the kernel's prologue
+  a.fold = a.per_sample ? nullptr : t3d_take_fold(a.alpha);
   // (forcing 3-4 waves/SIMD through launch bounds spills to scratch: 3-7x slower)
   // (a 6-row prefetch ring needs AGPR spill space -> 1 wave/SIMD: 40 % slower; PMC: VALU busy 46 %, memory unit stalled
   //  0.1 % -- the kernel is bound by the latency two resident waves per SIMD can hide)
@@ -806,15 +569,12 @@ int launch_s1c(Dw3BArgs& a, hipStream_t st) {
     if (a.res) T3D_LAUNCH_TIMED((dw3_bwd2_kernel<T, PF, 256, CH, ACTV, true>), grid, dim3(256), lds, st, a);        \
     else T3D_LAUNCH_TIMED((dw3_bwd2_kernel<T, PF, 256, CH, ACTV, false>), grid, dim3(256), lds, st, a);             \
   } while (0)
-  if (two_col) {
-    switch (a.act) {
-      case T3D_ACT_RELU: T3D_DWB2(T3D_ACT_RELU); break;
-      case T3D_ACT_RELU6: T3D_DWB2(T3D_ACT_RELU6); break;
-      case T3D_ACT_HSWISH: T3D_DWB2(T3D_ACT_HSWISH); break;
-      default: T3D_DWB2(T3D_ACT_NONE); break;
-    }
+  switch (a.act) {
+    case T3D_ACT_RELU: T3D_DWB2(T3D_ACT_RELU); break;
+    case T3D_ACT_RELU6: T3D_DWB2(T3D_ACT_RELU6); break;
+    case T3D_ACT_HSWISH: T3D_DWB2(T3D_ACT_HSWISH); break;
+    default: T3D_DWB2(T3D_ACT_NONE); break;
   }
-  else T3D_LAUNCH_TIMED((dw3_bwd_s1_kernel<T, CH, PF>), grid, dim3(256), lds, st, a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
@@ -1174,14 +934,7 @@ int launch_s2(Dw3BArgs& a, hipStream_t st) {
     a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
   }
   const size_t lds = (size_t)22 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64
-  // (in front of t3d_take_fold: a refused launch leaves the pending finalize request to the tiled fallback)
-  if ((size_t)a.B * a.H * a.W * a.C * sizeof(T) >= (1ull << 31)) return T3D_ERR_UNSUPPORTED;     // 32-bit buffer offsets
-  if (!a.per_sample) {
-    a.fold = t3d_take_fold(a.alpha);
-  } else {
-    if (const int rc = t3d_fold_fallback(a.alpha, st)) return rc;
-    a.fold = nullptr;
-  }
+  a.fold = a.per_sample ? nullptr : t3d_take_fold(a.alpha);
   switch (a.act) {
     case T3D_ACT_RELU: T3D_LAUNCH_TIMED((dw3_bwd_s2_kernel<T, PF, 256, T3D_ACT_RELU>), grid, dim3(256), lds, st, a); break;
     case T3D_ACT_RELU6: T3D_LAUNCH_TIMED((dw3_bwd_s2_kernel<T, PF, 256, T3D_ACT_RELU6>), grid, dim3(256), lds, st, a); break;
@@ -1194,23 +947,21 @@ int launch_s2(Dw3BArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// Called by t3d_dwconv_bwd for k == 3, stride 1 or 2.
-int t3d_dw3_bwd_stream(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                       const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int H,
-                       int W, int C, int stride, hipStream_t st) {
-  if (stride != 1 && stride != 2) return T3D_ERR_UNSUPPORTED;
+// T3D_DW_ROW3 backward: 3x3, both strides, tensors below 2 GB -- the kernels address through 32-bit buffer offsets, and the
+// dropped-lane sentinel 0x80000000 has to stay out of range
+bool t3d_dw_row3_bwd_can(const DwShape& s) {
+  return s.k == 3 && s.stride_1_or_2() && !s.gated && s.f32_or_bf16() && s.bytes() < (1ull << 31);
+}
+
+int t3d_dw_row3_bwd(const DwShape& s, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
+                    const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, hipStream_t st) {
+  if (!t3d_dw_row3_bwd_can(s)) return T3D_ERR_ARG;
   Dw3BArgs a{};
   a.dz = dz; a.y = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
   a.stats = stats; a.dw = dw;
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  if (stride == 2) {
-    if (dtype == T3D_F32) return launch_s2<float>(a, st);
-    if (dtype == T3D_BF16) return launch_s2<bf16_t>(a, st);
-    return T3D_ERR_ARG;
-  }
-  if (dtype == T3D_F32) return launch_s1<float>(a, st);
-  if (dtype == T3D_BF16) return launch_s1<bf16_t>(a, st);
-  return T3D_ERR_ARG;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
+  if (s.stride == 2) return s.dtype == T3D_F32 ? launch_s2<float>(a, st) : launch_s2<bf16_t>(a, st);
+  return s.dtype == T3D_F32 ? launch_s1<float>(a, st) : launch_s1<bf16_t>(a, st);
 }

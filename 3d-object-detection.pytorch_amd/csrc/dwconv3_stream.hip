@@ -15,7 +15,7 @@
 //     for its whole chunk, meet in LDS once per block and leave as one fp64 atomic per channel.
 // The 9 x 8 weights of the thread's channels live in registers for the whole walk.
 #include <cstdlib>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -584,9 +584,9 @@ __global__ __launch_bounds__(256) void dw3_fwd2_kernel(const Dw3Args a) {
   }
 }
 
-template <typename T, int CH>
-int launch_ch(Dw3Args& a, int s, hipStream_t st) {
-  constexpr int PF = 3;
+template <typename T>
+int launch(Dw3Args& a, int s, hipStream_t st) {
+  constexpr int PF = 3, CH = 4;
   const int CG = a.C / CH;
   // row chunks: enough work items to fill the chip (several resident waves per SIMD), but long enough that
   // the 1-2 halo rows re-read per chunk stay a small fraction
@@ -598,9 +598,8 @@ int launch_ch(Dw3Args& a, int s, hipStream_t st) {
   if (nchunks < 1) nchunks = 1;
   a.rows_per_chunk = cdiv(a.Ho, nchunks);
   a.nchunks = cdiv(a.Ho, a.rows_per_chunk);
-  const bool two_col = true;
   // (the two-column kernel addresses through 32-bit buffer offsets: tensors below 2 GB)
-  const bool use2 = (s == 1 && CH == 4 && two_col && (size_t)a.B * a.H * a.W * a.C * sizeof(T) < (1ull << 31));
+  const bool use2 = (s == 1 && (size_t)a.B * a.H * a.W * a.C * sizeof(T) < (1ull << 31));
   const int Wcols = use2 ? (a.Wo + 1) / 2 : a.Wo;     // work items per row: column pairs or columns
   dim3 grid;
   // persistent blocks: enough to fill the chip, few enough that the per-block flush stays cheap (tools/sweep_dwf.sh)
@@ -656,25 +655,24 @@ int launch_ch(Dw3Args& a, int s, hipStream_t st) {
   return T3D_OK;
 }
 
-template <typename T>
-int launch(Dw3Args& a, int s, hipStream_t st) {
-  const int ch = 4;
-  return ch == 8 ? launch_ch<T, 8>(a, s, st) : launch_ch<T, 4>(a, s, st);
-}
-
 }  // namespace
 
-// Called by t3d_dwconv_fwd for k == 3 without a squeeze-excite pooled output.
-int t3d_dw3_fwd_stream(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats, int B,
-                       int H, int W, int C, int stride, hipStream_t st) {
+// T3D_DW_ROW3 forward: 3x3 without pooled sums, all three storage types (fp16: inference); never refuses for size -- at 2 GB
+// and above it walks one column per thread instead of two
+bool t3d_dw_row3_fwd_can(const DwShape& s) {
+  return s.k == 3 && s.stride_1_or_2() && !s.pooled && !s.gated && (s.f32_or_bf16() || s.dtype == T3D_F16);
+}
+
+int t3d_dw_row3_fwd(const DwShape& s, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats,
+                    float*, hipStream_t st) {
+  if (!t3d_dw_row3_fwd_can(s)) return T3D_ERR_ARG;
   Dw3Args a{};
   a.x = x; a.y = y; a.w = w; a.stats = stats;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  a.Ho = (H + 2 - 3) / stride + 1;
-  a.Wo = (W + 2 - 3) / stride + 1;
-  if (dtype == T3D_F32) return launch<float>(a, stride, st);
-  if (dtype == T3D_BF16) return launch<bf16_t>(a, stride, st);
-  if (dtype == T3D_F16) return launch<f16_t>(a, stride, st);       // inference forward
-  return T3D_ERR_ARG;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
+  a.Ho = (s.H + 2 - 3) / s.stride + 1;
+  a.Wo = (s.W + 2 - 3) / s.stride + 1;
+  if (s.dtype == T3D_F32) return launch<float>(a, s.stride, st);
+  if (s.dtype == T3D_BF16) return launch<bf16_t>(a, s.stride, st);
+  return launch<f16_t>(a, s.stride, st);
 }

@@ -9,7 +9,7 @@
 // (oh, ow) and every pair belongs to exactly one thread: 25 + 25 packed FMAs per four input pixels, the full-resolution
 // x read once, dx written once, the quarter-resolution dz / y read three times (neighbour columns; L1 / L2).
 #include <cstdlib>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -447,8 +447,8 @@ int launch5_s1(Dw5BArgs& a, hipStream_t st) {
     a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
     a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
   }
-  const size_t lds = (size_t)54 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [27][Cb] fp64
-  if (lds > 64 * 1024) return T3D_ERR_UNSUPPORTED;
+  // [27][Cb] fp64: 27 KB for a slab; the flat mapping has fewer than 128 channels or was just checked to fit
+  const size_t lds = (size_t)54 * (a.slab ? 64 * CH : a.C) * sizeof(float);
   T3D_LAUNCH_TIMED((dw5_bwd_s1_kernel<T>), grid, dim3(256), lds, st, a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
@@ -494,8 +494,8 @@ int launch5_s2(Dw5BArgs& a, hipStream_t st) {
     a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
     a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
   }
-  const size_t lds = (size_t)54 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [27][Cb] fp64
-  if (lds > 64 * 1024) return T3D_ERR_UNSUPPORTED;
+  // [27][Cb] fp64: 27 KB for a slab; the flat mapping has fewer than 128 channels or was just checked to fit
+  const size_t lds = (size_t)54 * (a.slab ? 64 * CH : a.C) * sizeof(float);
   T3D_LAUNCH_TIMED((dw5_bwd_s2_kernel<T, PF>), grid, dim3(256), lds, st, a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
@@ -503,20 +503,18 @@ int launch5_s2(Dw5BArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// Called by t3d_dwconv_bwd for k == 5 (both strides; T3D_DW_TILED=1 keeps the LDS-tiled kernel of dwconv_bwd.hip).
-int t3d_dw5_bwd_stream(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                       const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int H,
-                       int W, int C, int stride, hipStream_t st) {
-  if (stride != 1 && stride != 2) return T3D_ERR_UNSUPPORTED;
-  if (C % 2) return T3D_ERR_UNSUPPORTED;
-  if (const int rc = t3d_fold_fallback(bb->alpha, st)) return rc;     // no derive prologue in the 5x5 kernels
+// T3D_DW_ROWK backward: 5x5, both strides, any plane and channel count (the reduction scratch always fits LDS, see the launchers)
+bool t3d_dw_rowk_bwd_can(const DwShape& s) { return s.k == 5 && s.stride_1_or_2() && !s.gated && s.f32_or_bf16(); }
+
+int t3d_dw_rowk_bwd(const DwShape& s, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
+                    const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, hipStream_t st) {
+  if (!t3d_dw_rowk_bwd_can(s)) return T3D_ERR_ARG;
   Dw5BArgs a{};
   a.dz = dz; a.y = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
   a.stats = stats; a.dw = dw;
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  if (dtype == T3D_F32) return stride == 2 ? launch5_s2<float>(a, st) : launch5_s1<float>(a, st);
-  if (dtype == T3D_BF16) return stride == 2 ? launch5_s2<bf16_t>(a, st) : launch5_s1<bf16_t>(a, st);
-  return T3D_ERR_ARG;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
+  if (s.dtype == T3D_F32) return s.stride == 2 ? launch5_s2<float>(a, st) : launch5_s1<float>(a, st);
+  return s.stride == 2 ? launch5_s2<bf16_t>(a, st) : launch5_s1<bf16_t>(a, st);
 }

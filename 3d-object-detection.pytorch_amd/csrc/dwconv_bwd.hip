@@ -12,8 +12,7 @@
 //          OUTPUT pixels; k*8 accumulators live in registers across the block's whole
 //          (persistent) tile loop and leave as fp32 atomics once per block.
 // Algorithmic traffic: read x, dz, y once, write dx once = 2*(in + out) elements.
-#include <cstdlib>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -275,8 +274,7 @@ int launch(const DwBwdArgs& a0, int k, int s, hipStream_t st) {
   // interior input region = (TH*s) x (TW*s); aim at ~nslots strips of 4 input pixels
   a.TW = (a.Wo * s >= 16) ? 16 / s : ((a.Wo + 3) / 4) * 4;
   if (a.TW * s % 4) a.TW = ((a.TW + 3) / 4) * 4;
-  const int th_mul = 1;
-  a.TH = th_mul * (nslots * 4) / (a.TW * s * s);
+  a.TH = (nslots * 4) / (a.TW * s * s);
   if (a.TH < 1) a.TH = 1;
   if (a.TH > a.Ho) a.TH = a.Ho;
   a.pix_stride = a.cgb * 8 + 8;
@@ -296,7 +294,6 @@ int launch(const DwBwdArgs& a0, int k, int s, hipStream_t st) {
   a.d_off = a.a_off + (int)abytes;
   size_t lds = a.d_off + dbytes;
   if (lds < a.a_off + scratch) lds = a.a_off + scratch;
-  if (lds > 160 * 1024) return T3D_ERR_UNSUPPORTED;
   a.tiles_x = cdiv(a.Wo, a.TW);
   a.tiles_y = cdiv(a.Ho, a.TH);
   const long long ntiles = (long long)a.B * a.tiles_x * a.tiles_y;
@@ -305,12 +302,10 @@ int launch(const DwBwdArgs& a0, int k, int s, hipStream_t st) {
   dim3 grid(gx, nchunks);
 #define T3D_DWB(KK, SS)                                                                             \
   if (k == KK && s == SS) {                                                                         \
-    if (lds > 64 * 1024)                                                                            \
-      (void)hipFuncSetAttribute((const void*)dw_bwd_kernel<T, KK, SS>,                              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
+    if (lds > 64 * 1024) (void)t3d_max_lds((const void*)dw_bwd_kernel<T, KK, SS>, (int)lds);        \
     T3D_LAUNCH_TIMED((dw_bwd_kernel<T, KK, SS>), grid, dim3(256), lds, st, a);                    \
   }
-  T3D_DWB(3, 1) else T3D_DWB(3, 2) else T3D_DWB(5, 1) else T3D_DWB(5, 2) else return T3D_ERR_UNSUPPORTED;
+  T3D_DWB(3, 1) else T3D_DWB(3, 2) else T3D_DWB(5, 1) else T3D_DWB(5, 2) else return T3D_ERR_ARG;
 #undef T3D_DWB
   T3D_CHECK_LAUNCH();
   return T3D_OK;
@@ -318,62 +313,17 @@ int launch(const DwBwdArgs& a0, int k, int s, hipStream_t st) {
 
 }  // namespace
 
-int t3d_dw3_bwd_stream(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                       const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int H,
-                       int W, int C, int stride, hipStream_t st);   // dwconv3_bwd_stream.hip
-
-int t3d_dw5_bwd_stream(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                       const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int H,
-                       int W, int C, int stride, hipStream_t st);   // dwconv5_bwd_stream.hip
-
-int t3d_dw5_plane7_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                       const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int C,
-                       hipStream_t st);   // dwconv5_plane7.hip
-
-int t3d_dw_tile_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                    const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int H, int W, int C,
-                    int k, int stride, hipStream_t st);   // dwconv_tile.hip
-
-extern "C" int t3d_dwconv_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w,
-                              const void* x, const t3d_prologue* pro, const void* residual, void* dx, double* stats,
-                              float* dw, int B, int H, int W, int C, int k, int stride, void* stream) {
-  if (!dz || !y || !bb || !w || !x || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8)) return T3D_ERR_ARG;
-  if (pro && pro->se) return T3D_ERR_UNSUPPORTED;  // no SE gate ever precedes a depthwise conv
-  if (k == 3 && !getenv("T3D_DW_TILED")) {   // small planes: register tiles (dwconv_tile.hip)
-    const int rc = t3d_dw_tile_bwd(dtype, dz, y, bb, w, x, pro, residual, dx, stats, dw, B, H, W, C, 3, stride, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if (k == 3 && (stride == 1 || stride == 2) && !getenv("T3D_DW_TILED")) {   // streaming kernel (dwconv3_bwd_stream.hip)
-    const int rc = t3d_dw3_bwd_stream(dtype, dz, y, bb, w, x, pro, residual, dx, stats, dw, B, H, W, C, stride,
-                                      reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if (k == 5 && stride == 1 && H == 7 && W == 7 && !getenv("T3D_DW_TILED")) {   // 7x7 planes in registers (dwconv5_plane7.hip)
-    const int rc = t3d_dw5_plane7_bwd(dtype, dz, y, bb, w, x, pro, residual, dx, stats, dw, B, C, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if (k == 5 && !getenv("T3D_DW_TILED")) {   // register tiles (dwconv_tile.hip)
-    const int rc = t3d_dw_tile_bwd(dtype, dz, y, bb, w, x, pro, residual, dx, stats, dw, B, H, W, C, 5, stride, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if (k == 5 && !getenv("T3D_DW_TILED")) {   // 5x5: streaming kernels (dwconv5_bwd_stream.hip)
-    const int rc = t3d_dw5_bwd_stream(dtype, dz, y, bb, w, x, pro, residual, dx, stats, dw, B, H, W, C, stride,
-                                      reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  // the tiled kernel reads finished coefficients: a pending derive request for them becomes a launch of its own
-  if (const int rc = t3d_fold_fallback(bb->alpha, reinterpret_cast<hipStream_t>(stream))) return rc;
+int t3d_dw_lds_bwd(const DwShape& s, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
+                   const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, hipStream_t st) {
+  if (!t3d_dw_lds_can(s)) return T3D_ERR_ARG;   // (dwconv_fwd.hip)
   DwBwdArgs a{};
   a.dz = dz; a.y = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
   a.stats = stats; a.dw = dw;
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  const int pad = (k - 1) / 2;
-  a.Ho = (H + 2 * pad - k) / stride + 1;
-  a.Wo = (W + 2 * pad - k) / stride + 1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == T3D_F32) return launch<float>(a, k, stride, st);
-  if (dtype == T3D_BF16) return launch<bf16_t>(a, k, stride, st);
-  return T3D_ERR_ARG;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
+  const int pad = (s.k - 1) / 2;
+  a.Ho = (s.H + 2 * pad - s.k) / s.stride + 1;
+  a.Wo = (s.W + 2 * pad - s.k) / s.stride + 1;
+  return s.dtype == T3D_F32 ? launch<float>(a, s.k, s.stride, st) : launch<bf16_t>(a, s.k, s.stride, st);
 }

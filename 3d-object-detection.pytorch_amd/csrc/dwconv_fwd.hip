@@ -10,8 +10,7 @@
 //   * per-channel sum / sum-of-squares for the following BatchNorm are kept in
 //     registers across the block's (persistent) tile loop and leave as ONE fp64
 //     atomic per channel per block.
-#include <cstdlib>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -227,7 +226,6 @@ int launch(const DwFwdArgs& a0, int k, int s, hipStream_t st) {
     if (a.tile_off + tile_bytes <= 64 * 1024 || a.TH == 1) break;
     a.TH = (a.TH + 1) / 2;
   }
-  if (a.tile_off + tile_bytes > 160 * 1024) return T3D_ERR_UNSUPPORTED;
   a.tiles_x = cdiv(a.Wo, a.TW);
   a.tiles_y = cdiv(a.Ho, a.TH);
   const size_t lds = a.tile_off + (tile_bytes > scratch ? tile_bytes : scratch);
@@ -237,12 +235,10 @@ int launch(const DwFwdArgs& a0, int k, int s, hipStream_t st) {
   dim3 grid(gx, nchunks);
 #define T3D_DW(KK, SS)                                                                          \
   if (k == KK && s == SS) {                                                                     \
-    if (lds > 64 * 1024)                                                                        \
-      (void)hipFuncSetAttribute((const void*)dw_fwd_kernel<T, KK, SS>,                                \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
+    if (lds > 64 * 1024) (void)t3d_max_lds((const void*)dw_fwd_kernel<T, KK, SS>, (int)lds);    \
     T3D_LAUNCH_TIMED((dw_fwd_kernel<T, KK, SS>), grid, dim3(256), lds, st, a);                \
   }
-  T3D_DW(3, 1) else T3D_DW(3, 2) else T3D_DW(5, 1) else T3D_DW(5, 2) else return T3D_ERR_UNSUPPORTED;
+  T3D_DW(3, 1) else T3D_DW(3, 2) else T3D_DW(5, 1) else T3D_DW(5, 2) else return T3D_ERR_ARG;
 #undef T3D_DW
   T3D_CHECK_LAUNCH();
   return T3D_OK;
@@ -250,58 +246,24 @@ int launch(const DwFwdArgs& a0, int k, int s, hipStream_t st) {
 
 }  // namespace
 
-int t3d_dw3_fwd_stream(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats, int B,
-                       int H, int W, int C, int stride, hipStream_t st);   // dwconv3_stream.hip
+// T3D_DW_LDS, both directions (the backward kernel of dwconv_bwd.hip has the same limits): the one family that applies a
+// squeeze-excite gate on load.  No shape is refused for its LDS: the launchers halve the tile height until weights + tiles
+// fit 64 KB, and one-row tiles always do (fp32, 5x5, 72 staged channels: forward 5 x 35 pixels at stride 2 = 50.4 KB + 6.4 KB
+// of weights; backward 5 x 20 pixels of input and of gradient at stride 1 = 2 x 28.8 KB + 6.4 KB = 64000 bytes).
+bool t3d_dw_lds_can(const DwShape& s) {
+  return s.f32_or_bf16() && (s.k == 3 || s.k == 5) && s.stride_1_or_2() && !(s.backward && s.gated);
+}
 
-int t3d_dwk_fwd_stream(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats,
-                       float* gap_sum, int B, int H, int W, int C, int k, int stride, hipStream_t st);   // dwconvk_stream.hip
-
-int t3d_dw5_plane7_fwd(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats, float* gap_sum,
-                       int B, int C, hipStream_t st);   // dwconv5_plane7.hip
-
-int t3d_dw_tile_fwd(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats, float* gap_sum,
-                    int B, int H, int W, int C, int k, int stride, hipStream_t st);   // dwconv_tile.hip
-
-extern "C" int t3d_dwconv_fwd(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y,
-                              double* stats, float* gap_sum, int B, int H, int W, int C, int k, int stride,
-                              void* stream) {
-  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8)) return T3D_ERR_ARG;
-  if (k == 3 && !getenv("T3D_DW_TILED")) {
-    // 3x3 on the small planes (14x14 and below by default): register tiles, every load of a tile's window up front (dwconv_tile.hip)
-    const int rc = t3d_dw_tile_fwd(dtype, x, pro, w, y, stats, gap_sum, B, H, W, C, 3, stride, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if (k == 3 && (stride == 1 || stride == 2) && !gap_sum && !(pro && pro->se) && !getenv("T3D_DW_TILED"))
-    return t3d_dw3_fwd_stream(dtype, x, pro, w, y, stats, B, H, W, C, stride, reinterpret_cast<hipStream_t>(stream));
-  // the kernels below read finished coefficients: a pending derive request for them becomes a launch of its own
-  if (pro)
-    if (const int rc = t3d_fold_fallback(pro->scale, reinterpret_cast<hipStream_t>(stream))) return rc;
-  if (k == 5 && stride == 1 && H == 7 && W == 7 && !getenv("T3D_DW_TILED")) {
-    // 5x5 on 7x7 planes (the 1/32 stage of MobileNetV3): a thread per (image, channel pair) holds the plane (dwconv5_plane7.hip)
-    const int rc = t3d_dw5_plane7_fwd(dtype, x, pro, w, y, stats, gap_sum, B, C, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if (k == 5 && !getenv("T3D_DW_TILED")) {
-    // 5x5 on planes up to 64x64: register tiles, every load of a tile's window up front (dwconv_tile.hip)
-    const int rc = t3d_dw_tile_fwd(dtype, x, pro, w, y, stats, gap_sum, B, H, W, C, 5, stride, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  if ((k == 3 || k == 5) && (stride == 1 || stride == 2) && !(pro && pro->se) && !getenv("T3D_DW_TILED")) {
-    // 5x5 layers and the squeeze-excite blocks (per-sample pooled sums): generic streaming kernel
-    const int rc = t3d_dwk_fwd_stream(dtype, x, pro, w, y, stats, gap_sum, B, H, W, C, k, stride,
-                                      reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
+int t3d_dw_lds_fwd(const DwShape& s, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats,
+                   float* gap_sum, hipStream_t st) {
+  if (!t3d_dw_lds_can(s)) return T3D_ERR_ARG;
   DwFwdArgs a{};
   a.x = x; a.y = y; a.w = w;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.se = pro->se; a.act = pro->act; a.se_after = pro->se_after_act; }
   a.stats = stats; a.gap = gap_sum; a.gapq = g_t3d_reduce.pool_exact;
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  const int pad = (k - 1) / 2;
-  a.Ho = (H + 2 * pad - k) / stride + 1;
-  a.Wo = (W + 2 * pad - k) / stride + 1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == T3D_F32) return launch<float>(a, k, stride, st);
-  if (dtype == T3D_BF16) return launch<bf16_t>(a, k, stride, st);
-  return T3D_ERR_ARG;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
+  const int pad = (s.k - 1) / 2;
+  a.Ho = (s.H + 2 * pad - s.k) / s.stride + 1;
+  a.Wo = (s.W + 2 * pad - s.k) / s.stride + 1;
+  return s.dtype == T3D_F32 ? launch<float>(a, s.k, s.stride, st) : launch<bf16_t>(a, s.k, s.stride, st);
 }

@@ -13,7 +13,7 @@
 // data gradient first, weight gradient second (plane kernel's two phases, for the same register reason).
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -637,65 +637,49 @@ int launch_bwd(TileArgs& a, int act, int stride, hipStream_t st) {
 }
 #undef T3D_TILE_ACT
 
-// which planes take the tile kernels (isolated, B = 256, us tile | row walk; profiles/r6_*_dw5_isolated.txt, _dw3_small_planes_*):
+}  // namespace
+
+// can: both stencils, both strides, any plane of at least 2 x 2 (the windows clamp their loads into the plane) -- 5x5 from 8 x 8:
+// smaller 5x5 planes have never run on the tiles (7 x 7 is the plane kernel's, dwconv5_plane7.hip).  No gate, no fp16.
+bool t3d_dw_tile_can(const DwShape& s) {
+  const int lo = s.k == 5 ? 8 : 2;
+  return (s.k == 3 || s.k == 5) && s.stride_1_or_2() && !s.gated && s.f32_or_bf16() && s.H >= lo && s.W >= lo;
+}
+
+// wanted: which planes take the tile kernels (isolated, B = 256, us tile | row walk; profiles/r6_*_dw5_isolated.txt, _dw3_small_planes_*):
 //   5x5 s1 28x28x120: forward 48 | 58 (79 before the chunk fix), backward 116 | 185;  5x5 s2 14x14x672: 55 | 74, 117 | 163;
 //   5x5 s2 56x56x72: 96 | 90, 171 | 178 -- no gain, stays on the walk;  7x7 planes: dwconv5_plane7.hip (17 | 67, 50 | 116).
 //   3x3: the tiles LOSE to the row-walk kernels of dwconv3_stream.hip / dwconv3_bwd_stream.hip on every plane of MobileNetV2
 //   (28x28x192: 50 | 36 forward, 127 | 85 backward; 14x14x384: 27 | 24, 66 | 42; 7x7x960: 18 | 19, 47 | 34) -- those kernels
-//   are at 3.2-4.4 TB/s alone, their in-step times are contention, not structure.  OPT-IN: T3D_DW3_TILE_MAX = largest plane side.
-static int dw3_tile_max() {      // (read per call: the test suite flips it inside one process, like T3D_DW_TILED)
-  const char* e = getenv("T3D_DW3_TILE_MAX");
-  return e ? atoi(e) : 0;
-}
-static bool tile_shape_ok(int k, int stride, int H, int W, int C, bool pooled = false) {
-  if ((C % 2) || H < 2 || W < 2) return false;
-  if (k == 5) return H >= 8 && W >= 8 && H <= (stride == 2 ? 28 : 64) && W <= (stride == 2 ? 28 : 64);
-  // 3x3 forward WITH squeeze-excite pooled sums on the 14x14 stage and below: those launches go to the generic walk of
-  // dwconvk_stream.hip (the 3x3 row-walk kernel has no pooled sums), which the tiles beat: 14x14x480 52 -> 36 us, x672 59 -> 51
-  if (k == 3 && pooled && stride == 1 && H <= 14 && W <= 14) return true;
-  if (k == 3) return H <= dw3_tile_max() && W <= dw3_tile_max();
-  return false;
+//   are at 3.2-4.4 TB/s alone, their in-step times are contention, not structure -- with one exception:
+//   3x3 forward WITH squeeze-excite pooled sums on the 14x14 stage and below: those launches would go to the generic walk of
+//   dwconvk_stream.hip (the 3x3 row-walk kernel has no pooled sums), which the tiles beat: 14x14x480 52 -> 36 us, x672 59 -> 51
+bool t3d_dw_tile_wanted(const DwShape& s) {
+  if (s.k == 5) return s.H <= (s.stride == 2 ? 28 : 64) && s.W <= (s.stride == 2 ? 28 : 64);
+  return !s.backward && s.pooled && s.stride == 1 && s.H <= 14 && s.W <= 14;
 }
 
-}  // namespace
-
-int t3d_dw_tile_fwd(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats, float* gap_sum,
-                    int B, int H, int W, int C, int k, int stride, hipStream_t st) {
-  if (!tile_shape_ok(k, stride, H, W, C, gap_sum != nullptr) || (pro && pro->se) || (stride != 1 && stride != 2)) return T3D_ERR_UNSUPPORTED;
-  if (pro)
-    if (const int rc = t3d_fold_fallback(pro->scale, st)) return rc;      // finished coefficients (no derive prologue here)
+int t3d_dw_tile_fwd(const DwShape& s, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats,
+                    float* gap_sum, hipStream_t st) {
+  if (!t3d_dw_tile_can(s)) return T3D_ERR_ARG;
   TileArgs a{};
   a.x = x; a.y = y; a.w = w; a.stats = stats; a.gap = gap_sum; a.gapq = g_t3d_reduce.pool_exact;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; }
-  a.B = B; a.H = H; a.W = W; a.C = C;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
   const int act = pro ? pro->act : T3D_ACT_NONE;
-  if (k == 5) {
-    if (dtype == T3D_F32) return launch_fwd<float, 5>(a, act, stride, st);
-    if (dtype == T3D_BF16) return launch_fwd<bf16_t, 5>(a, act, stride, st);
-  } else {
-    if (dtype == T3D_F32) return launch_fwd<float, 3>(a, act, stride, st);
-    if (dtype == T3D_BF16) return launch_fwd<bf16_t, 3>(a, act, stride, st);
-  }
-  return T3D_ERR_UNSUPPORTED;
+  if (s.k == 5) return s.dtype == T3D_F32 ? launch_fwd<float, 5>(a, act, s.stride, st) : launch_fwd<bf16_t, 5>(a, act, s.stride, st);
+  return s.dtype == T3D_F32 ? launch_fwd<float, 3>(a, act, s.stride, st) : launch_fwd<bf16_t, 3>(a, act, s.stride, st);
 }
 
-int t3d_dw_tile_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
-                    const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, int B, int H, int W, int C,
-                    int k, int stride, hipStream_t st) {
-  if (!tile_shape_ok(k, stride, H, W, C) || (pro && pro->se) || (stride != 1 && stride != 2)) return T3D_ERR_UNSUPPORTED;
-  if (const int rc = t3d_fold_fallback(bb->alpha, st)) return rc;
+int t3d_dw_tile_bwd(const DwShape& s, const void* dz, const void* y, const t3d_bnbwd* bb, const float* w, const void* x,
+                    const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, hipStream_t st) {
+  if (!t3d_dw_tile_can(s)) return T3D_ERR_ARG;
   TileArgs a{};
   a.dz = dz; a.yraw = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; }
-  a.stats = stats; a.dw = dw; a.B = B; a.H = H; a.W = W; a.C = C;
+  a.stats = stats; a.dw = dw; a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
   const int act = pro ? pro->act : T3D_ACT_NONE;
-  if (k == 5) {
-    if (dtype == T3D_F32) return launch_bwd<float, 5>(a, act, stride, st);
-    if (dtype == T3D_BF16) return launch_bwd<bf16_t, 5>(a, act, stride, st);
-  } else {
-    if (dtype == T3D_F32) return launch_bwd<float, 3>(a, act, stride, st);
-    if (dtype == T3D_BF16) return launch_bwd<bf16_t, 3>(a, act, stride, st);
-  }
-  return T3D_ERR_UNSUPPORTED;
+  if (s.k == 5) return s.dtype == T3D_F32 ? launch_bwd<float, 5>(a, act, s.stride, st) : launch_bwd<bf16_t, 5>(a, act, s.stride, st);
+  return s.dtype == T3D_F32 ? launch_bwd<float, 3>(a, act, s.stride, st) : launch_bwd<bf16_t, 3>(a, act, s.stride, st);
 }

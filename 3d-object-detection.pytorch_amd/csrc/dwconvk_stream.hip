@@ -14,7 +14,7 @@
 // (wave-uniform); loads are unconditional from clamped addresses.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "dwconv_route.h"
 
 namespace {
 
@@ -256,24 +256,28 @@ int launch_t(DwkArgs& a, int k, int s, hipStream_t st) {
   if (k == 5 && s == 1) return launch_ks<T, 5, 1>(a, st);
   if (k == 5 && s == 2) return launch_ks<T, 5, 2>(a, st);
   if (k == 3 && s == 1) return launch_ks<T, 3, 1>(a, st);
-  if (k == 3 && s == 2) return launch_ks<T, 3, 2>(a, st);
-  return T3D_ERR_UNSUPPORTED;
+  return launch_ks<T, 3, 2>(a, st);
 }
 
 }  // namespace
 
-// Called by t3d_dwconv_fwd for k = 5, and for k = 3 with squeeze-excite pooled sums (no SE gate on the INPUT).
-int t3d_dwk_fwd_stream(int dtype, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats,
-                       float* gap_sum, int B, int H, int W, int C, int k, int stride, hipStream_t st) {
+// T3D_DW_ROWK forward: the generic walk -- the 5x5 layers the plane and tile kernels leave, and 3x3 with squeeze-excite pooled
+// sums (no SE gate on the INPUT); all three storage types (fp16: the 5x5 layers of the MobileNetV3 layouts at inference)
+bool t3d_dw_rowk_fwd_can(const DwShape& s) {
+  return (s.k == 3 || s.k == 5) && s.stride_1_or_2() && !s.gated && (s.f32_or_bf16() || s.dtype == T3D_F16);
+}
+
+int t3d_dw_rowk_fwd(const DwShape& s, const void* x, const t3d_prologue* pro, const float* w, void* y, double* stats,
+                    float* gap_sum, hipStream_t st) {
+  if (!t3d_dw_rowk_fwd_can(s)) return T3D_ERR_ARG;
   DwkArgs a{};
   a.x = x; a.y = y; a.w = w; a.stats = stats; a.gap = gap_sum; a.gapq = g_t3d_reduce.pool_exact;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  const int pad = (k - 1) / 2;
-  a.Ho = (H + 2 * pad - k) / stride + 1;
-  a.Wo = (W + 2 * pad - k) / stride + 1;
-  if (dtype == T3D_F32) return launch_t<float>(a, k, stride, st);
-  if (dtype == T3D_BF16) return launch_t<bf16_t>(a, k, stride, st);
-  if (dtype == T3D_F16) return launch_t<f16_t>(a, k, stride, st);       // inference forward (the 5x5 layers of the MobileNetV3 layouts)
-  return T3D_ERR_ARG;
+  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
+  const int pad = (s.k - 1) / 2;
+  a.Ho = (s.H + 2 * pad - s.k) / s.stride + 1;
+  a.Wo = (s.W + 2 * pad - s.k) / s.stride + 1;
+  if (s.dtype == T3D_F32) return launch_t<float>(a, s.k, s.stride, st);
+  if (s.dtype == T3D_BF16) return launch_t<bf16_t>(a, s.k, s.stride, st);
+  return launch_t<f16_t>(a, s.k, s.stride, st);
 }

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get('T3D_LIB') or os.path.join(os.path.dirname(_HERE), 'li
 W_FRAG = 0x100                  # include/t3d.h: T3D_W_FRAG (weights in fragment order, bf16 pointwise convs)
 F32, BF16, F16 = 0, 1, 2        # include/t3d.h: T3D_F32 / T3D_BF16 / T3D_F16 (fp16: inference forward only)
 ACT = {'none': 0, 'relu': 1, 'relu6': 2, 'hswish': 3}
+DW_AUTO, DW_TILE, DW_ROW3, DW_PLANE7, DW_ROWK, DW_LDS = -1, 0, 1, 2, 3, 4      # include/t3d.h: T3D_DW_* (depthwise kernel families)
+ERR_ARG, ERR_UNSUPPORTED = -1, -3
 POOL = {'avg': 0, 'max': 1, 'avg+max': 2}
 _P, _I, _F, _D, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
 
@@ -64,6 +66,8 @@ SIGNATURES = {
     't3d_set_launch_events': [_P, _P],
     't3d_sum_slots_batched': [_P, _I, _P],
     't3d_dwconv_bwd': [_I, _P, _P, _BP, _P, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    't3d_dwconv_route': [_I] * 10,
+    't3d_dwconv_force_route': [_I],
     't3d_pwconv_wgrad': [_I, _P, _P, _BP, _P, _PP, _P, _I, _I, _I, _I, _P],
     't3d_pwconv_yfree_prep': [_P, _BP, _P, _P, _I, _I, _P],
     't3d_pwconv_dgrad_yfree': [_P, _P, _P, _P, _P, _PP, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -188,6 +188,22 @@ int t3d_dwconv_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb
                    const void* x, const t3d_prologue* pro, const void* residual, void* dx, double* stats,
                    float* dw, int B, int H, int W, int C, int k, int stride, void* stream);
 
+/* Which kernel family a depthwise call takes.  Both entry points pick it once, ahead of any side effect, by a pure function
+ * of the call's shape: a call that returns an error has launched nothing and has left a pending t3d_fold_request pending.
+ *   T3D_DW_TILE    register tiles (csrc/dwconv_tile.hip): 5x5 on 8x8 ... 64x64 planes (28x28 at stride 2), pooled 3x3 up to 14x14
+ *   T3D_DW_ROW3    3x3 row walk (csrc/dwconv3_stream.hip, dwconv3_bwd_stream.hip; backward: tensors below 2 GB)
+ *   T3D_DW_PLANE7  5x5 stride 1 on 7x7 planes (csrc/dwconv5_plane7.hip)
+ *   T3D_DW_ROWK    k x k row walk (csrc/dwconvk_stream.hip; backward 5x5: dwconv5_bwd_stream.hip)
+ *   T3D_DW_LDS     LDS tiles (csrc/dwconv_fwd.hip, dwconv_bwd.hip): the only family with a gated input
+ * t3d_dwconv_route RETURNS the route id of such a call, or the negative T3D_ERR_* the entry point would return; it makes no
+ * device call.  gated_input: a squeeze-excite gate in the input prologue (pro->se); pooled: gap_sum != NULL (forward only).
+ * t3d_dwconv_force_route (tests and timing tools only; process-wide, T3D_DW_AUTO clears it): while a route is forced, the
+ * query and both entry points take that family wherever its kernels are correct -- measured faster or not -- and return
+ * T3D_ERR_UNSUPPORTED, launching nothing, where they are not. */
+enum { T3D_DW_AUTO = -1, T3D_DW_TILE = 0, T3D_DW_ROW3 = 1, T3D_DW_PLANE7 = 2, T3D_DW_ROWK = 3, T3D_DW_LDS = 4 };
+int t3d_dwconv_route(int backward, int dtype, int gated_input, int pooled, int B, int H, int W, int C, int k, int stride);
+int t3d_dwconv_force_route(int route);
+
 /* BatchNorm backward bookkeeping: from the reductions the gradient-producing kernel emitted,
  *   stats [2*C] fp64 = sum(dz), sum(dz*y)  over `count` elements (dz: gradient at the BN output,
  *   y: raw BN input), and the forward's mean / invstd, build the backward affine

@@ -168,16 +168,14 @@ def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
 
 @pytest.mark.parametrize('B,C,H,W,k,s', [(8, 32, 56, 56, 3, 1), (4, 144, 28, 28, 3, 1), (4, 192, 28, 28, 3, 2), (2, 960, 7, 7, 3, 1),
                                          (4, 120, 28, 28, 5, 1), (4, 240, 14, 14, 5, 2), (2, 48, 14, 14, -5, 1), (6, 960, 7, 7, 5, 1)])
-def test_dwconv_bwd_weight_gradient_slots_are_exactly_reproducible(B, C, H, W, k, s, monkeypatch):
+def test_dwconv_bwd_weight_gradient_slots_are_exactly_reproducible(B, C, H, W, k, s):
     """t3d_set_dw_slots (include/t3d.h): every workgroup stores its partial depthwise weight gradient into its own slot and
     t3d_sum_slots_batched adds the used slots in index order -- same result as the atomic replica form to fp32 rounding,
     bit-identical from launch to launch (the atomic form is not), `used` = the slots the launch filled (or the replica count
-    for the kernels without slot support: k = -5 runs the 5x5 case through the LDS-tiled fallback, T3D_DW_TILED=1)."""
+    for the kernels without slot support: k = -5 runs the 5x5 case through the LDS-tiled fallback, forced route T3D_DW_LDS)."""
     from torchdet3d import _native as N
     tiled = k < 0
     k = abs(k)
-    if tiled:
-        monkeypatch.setenv('T3D_DW_TILED', '1')
     g = torch.Generator().manual_seed(C + k)
     dtype = torch.bfloat16
     Ho, Wo = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
@@ -193,10 +191,12 @@ def test_dwconv_bwd_weight_gradient_slots_are_exactly_reproducible(B, C, H, W, k
         N.call('t3d_dwconv_bwd', N.BF16, N.ptr(dz), N.ptr(y), bb, N.ptr(w), N.ptr(x), pro, None, N.ptr(dx), N.ptr(stats), N.ptr(dw),
                B, H, W, C, k, s, N.stream())
     ref, st_ref = torch.zeros(C, k * k, device='cuda'), torch.zeros(2 * C, device='cuda', dtype=torch.float64)
-    launch(ref, st_ref)                                           # plain form: one replica, atomics
     SLOTS = 512
     results = []
     try:
+        if tiled:
+            N.call('t3d_dwconv_force_route', N.DW_LDS)
+        launch(ref, st_ref)                                       # plain form: one replica, atomics
         for rep in range(3):
             slots = torch.full((SLOTS, C, k * k), float('nan'), device='cuda')
             slots[:16].zero_()                                    # what a launch without slot support adds into
@@ -212,6 +212,7 @@ def test_dwconv_bwd_weight_gradient_slots_are_exactly_reproducible(B, C, H, W, k
             torch.cuda.synchronize()
             results.append((out.clone(), int(used.item()), st16.sum(0)))
     finally:
+        N.call('t3d_dwconv_force_route', N.DW_AUTO)
         N.call('t3d_set_dw_slots', 0, None)
         N.call('t3d_set_reduction_replicas', 1, 0)
     out, nused, st = results[0]
@@ -280,11 +281,59 @@ def test_dwconv_bwd_refused_by_the_streaming_kernel_keeps_its_pending_finalize(s
 
 @pytest.mark.parametrize('B,C,H,W,k,s', [(2, 32, 24, 24, 3, 1), (2, 96, 24, 24, 3, 2), (5, 264, 9, 7, 3, 1), (3, 40, 13, 17, 3, 2), (2, 960, 7, 7, 3, 1)])
 @pytest.mark.parametrize('dt', ['f32', 'bf16'])
-def test_3x3_register_tiles_opt_in(B, C, H, W, k, s, dt, monkeypatch):
+def test_3x3_register_tiles_opt_in(B, C, H, W, k, s, dt):
     """The 3x3 instantiation of the register-tile kernels (csrc/dwconv_tile.hip) is opt-in -- it measured slower than the
-    row-walk kernels on every plane of MobileNetV2 -- but stays correct: the same forward / backward checks with
-    T3D_DW3_TILE_MAX covering the plane."""
-    monkeypatch.setenv('T3D_DW3_TILE_MAX', '64')
-    test_dwconv_fwd(B, C, H, W, k, s, dt, 'bnact')
-    test_dwconv_bwd(B, C, H, W, k, s, dt, 'bnact_ps')
-    test_dwconv_bwd(B, C, H, W, k, s, dt, 'plain_res')
+    row-walk kernels on every plane of MobileNetV2 -- but stays correct: the same forward / backward checks with the
+    route forced to T3D_DW_TILE."""
+    from torchdet3d import _native as N
+    N.call('t3d_dwconv_force_route', N.DW_TILE)
+    try:
+        test_dwconv_fwd(B, C, H, W, k, s, dt, 'bnact')
+        test_dwconv_bwd(B, C, H, W, k, s, dt, 'bnact_ps')
+        test_dwconv_bwd(B, C, H, W, k, s, dt, 'plain_res')
+    finally:
+        N.call('t3d_dwconv_force_route', N.DW_AUTO)
+
+
+def test_a_refused_dwconv_call_launches_nothing_and_keeps_the_pending_finalize():
+    """The kernel family is picked ahead of every side effect (csrc/dwconv_route.hip): a call the forced family cannot take
+    returns T3D_ERR_UNSUPPORTED with no kernel launched, the output untouched and the t3d_fold_request for its coefficients
+    still pending (a later launch can still honour it; a request consumed by a refused call leaves them uncomputed)."""
+    from torchdet3d import _native as N
+    B, H, W, C = 2, 9, 7, 264
+    dev, bf = 'cuda', torch.bfloat16
+    x, dz, y = (torch.randn(B, H, W, C, device=dev).to(bf) for _ in range(3))
+    w = torch.randn(C, 9, device=dev)
+    sc, sh = torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev)
+    al, be, ga = (torch.rand(C, device=dev) for _ in range(3))
+    pro, bb = N.prologue(sc, sh, None, 'relu6', False), N.bnbwd(al, be, ga, False)
+    st = torch.zeros(2 * C, device=dev, dtype=torch.float64)
+    mean, invstd, gamma = torch.zeros(C, device=dev), torch.ones(C, device=dev), torch.ones(C, device=dev)
+    spare = [torch.empty(C, device=dev) for _ in range(2)]
+
+    def fold(kind, o):       # a complete t3d_bn_fold in device memory (nobody may read it: the call is refused first)
+        f = N.BnFold()
+        f.kind, f.C, f.count, f.nrep, f.rstride, f.eps = kind, C, float(B * H * W), 1, 2 * C, 1e-5
+        f.gamma, f.stats, f.mean, f.invstd = N.ptr(gamma), N.ptr(st), N.ptr(mean), N.ptr(invstd)
+        f.o0, f.o1, f.o2, f.o3 = (N.ptr(t) for t in o)
+        return torch.frombuffer(bytearray(bytes(f)), dtype=torch.uint8).cuda()
+    descs = {1: fold(1, (sc, sh, *spare)), 2: fold(2, (al, be, ga, spare[0]))}
+    out = torch.full((B, H, W, C), 7.0, device=dev, dtype=bf)
+    lib = N.lib()
+    N.call('t3d_dwconv_force_route', N.DW_PLANE7)
+    try:
+        for kind, key, call in ((2, al, lambda: lib.t3d_dwconv_bwd(N.BF16, N.ptr(dz), N.ptr(y), bb, N.ptr(w), N.ptr(x), pro, None,
+                                                                   N.ptr(out), None, None, B, H, W, C, 3, 1, N.stream())),
+                                (1, sc, lambda: lib.t3d_dwconv_fwd(N.BF16, N.ptr(x), pro, N.ptr(w), N.ptr(out), None, None, B, H, W, C, 3, 1,
+                                                                   N.stream()))):
+            N.call('t3d_fold_request', N.ptr(descs[kind]), N.ptr(key))
+            before = N.launch_count()
+            rc = call()
+            assert rc == N.ERR_UNSUPPORTED
+            assert N.launch_count() == before
+            assert lib.t3d_fold_pending() == 1 and lib.t3d_fold_pending() == 0
+    finally:
+        lib.t3d_fold_pending()
+        N.call('t3d_dwconv_force_route', N.DW_AUTO)
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()

@@ -1,12 +1,13 @@
 """Profiling aid: launch ONE conv entry point repeatedly on a given shape (for rocprofv3 --pmc / --kernel-trace).
-usage: run_kernel.py dwfwd|dwbwd|pwfwd|pwdgrad|pwwgrad  B H W C [k s] | M HW K N   [--reps R] [--f32] [--res] [--gate]"""
+usage: run_kernel.py dwfwd|dwbwd|pwfwd|pwdgrad|pwwgrad  B H W C [k s] | M HW K N   [--reps R] [--f32] [--res] [--gate]
+       [--route tile|row3|plane7|rowk|lds]   (depthwise: t3d_dwconv_force_route instead of the automatic choice)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, '3d-object-detection.pytorch_amd')]
 import torch
 from torchdet3d import _native as N
 
-args = [a for i, a in enumerate(sys.argv[1:]) if not a.startswith('--') and sys.argv[i] not in ('--reps', '--nrep', '--act')]
+args = [a for i, a in enumerate(sys.argv[1:]) if not a.startswith('--') and sys.argv[i] not in ('--reps', '--nrep', '--act', '--route')]
 reps = int(sys.argv[sys.argv.index('--reps') + 1]) if '--reps' in sys.argv else 5
 dt = torch.float32 if '--f32' in sys.argv else torch.bfloat16
 nrep = int(sys.argv[sys.argv.index('--nrep') + 1]) if '--nrep' in sys.argv else 1
@@ -16,6 +17,8 @@ g = torch.Generator(device=dev).manual_seed(0)
 rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
 keep = []
 if kind in ('dwfwd', 'dwbwd'):
+    if '--route' in sys.argv:
+        N.call('t3d_dwconv_force_route', getattr(N, 'DW_' + sys.argv[sys.argv.index('--route') + 1].upper()))
     B, H, W, C = dims[:4]
     k, s = (dims[4], dims[5]) if len(dims) > 5 else (3, 1)
     Ho, Wo = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
