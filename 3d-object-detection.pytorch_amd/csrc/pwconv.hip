@@ -18,9 +18,8 @@
 //     sits in between).  Sums are reduced over the 16 pixels of a DPP row, parked in
 //     LDS across the block's persistent tile loop and leave as one fp64 atomic per
 //     channel per block.
-#include <cstdlib>
 #include <type_traits>
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 using namespace t3d_pw;
 
@@ -365,111 +364,14 @@ int launch(GemmArgs& a, hipStream_t st) {
   return launch_nt<T, 8>(a, st);  // wider outputs tile over grid.y (A re-read comes from L2)
 }
 
-int dispatch(int dtype, GemmArgs& a, void* stream) {
-  if (a.M <= 0 || a.Kin <= 0 || a.Nout <= 0 || (a.Kin % 8) || (a.Nout % 8) || a.HW <= 0) return T3D_ERR_ARG;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // `w` is the fragment-order copy (include/t3d.h: T3D_W_FRAG): the deep-contraction kernel where it takes the shape, else the
-  // streaming kernel; the LDS-tiled fallback below cannot read it
-  a.wfrag = (dtype & T3D_W_FRAG) ? 1 : 0;
-  dtype &= ~T3D_W_FRAG;
-  if (a.wfrag && dtype != T3D_BF16 && dtype != T3D_F16) return T3D_ERR_ARG;
-  if (dtype == T3D_BF16) {
-    int rc = (a.wfrag && deep_shape(a.Kin, a.Nout)) ? deep_launch(a, st) : T3D_ERR_UNSUPPORTED;
-    if (rc == T3D_ERR_UNSUPPORTED) rc = stream_launch(a, st);
-    if (rc != T3D_ERR_UNSUPPORTED || a.wfrag) return rc;
-  }
-  if (dtype == T3D_F16) {                    // inference forward in fp16 storage: the streaming kernel or nothing
-    if (const int rc = t3d_fold_fallback(a.p0, st)) return rc;
-    return stream_launch_f16(a, st);
-  }
-  // the LDS-tiled kernel reads finished coefficients: a pending derive request for them becomes a launch of its own
-  if (const int rc = t3d_fold_fallback(a.p0, st)) return rc;
-  if (dtype == T3D_F32) {
-    // inference forwards of many-pixel layers: the register-operand fp32 kernel (pwconv_f32_reg.hip; T3D_F32_TILED=1: round 1's)
-    const bool tiled = getenv("T3D_F32_TILED") != nullptr;
-    const int rc = tiled ? T3D_ERR_UNSUPPORTED : f32_reg_launch(a, st);
-    return rc != T3D_ERR_UNSUPPORTED ? rc : launch<float>(a, st);
-  }
-  if (dtype == T3D_BF16) return launch<bf16_t>(a, st);
-  return T3D_ERR_ARG;
-}
-
 }  // namespace
 
-extern "C" int t3d_pwconv_fwd(int dtype, const void* x, const t3d_prologue* pro, const void* w, const float* bias,
-                              void* y, double* stats, int M, int HW, int K, int N, void* stream) {
-  if (!x || !w || (!y && !stats)) return T3D_ERR_ARG;
-  GemmArgs a{};
-  a.a0 = x;
-  if (pro) { a.p0 = pro->scale; a.p1 = pro->shift; a.p2 = pro->se; a.act = pro->act; a.se_after = pro->se_after_act; }
-  a.w = w; a.bias = bias; a.out = y; a.stats = stats;
-  a.M = M; a.HW = HW; a.Kin = K; a.Nout = N;
-  if (!y) {
-    // statistics-only pass (the BatchNorm sums of a conv whose output is never stored: t3d_expdw_fwd recomputes it in
-    // LDS): bf16 streaming kernel only
-    a.wfrag = (dtype & T3D_W_FRAG) ? 1 : 0;
-    if ((dtype & ~T3D_W_FRAG) != T3D_BF16 || (K % 8) || (N % 8) || M <= 0 || HW <= 0) return T3D_ERR_UNSUPPORTED;
-    return stream_launch(a, reinterpret_cast<hipStream_t>(stream));
-  }
-  return dispatch(dtype, a, stream);
+// fp32 or bf16 storage, row-major weights: every forward with an output and every data gradient (the general kernel)
+bool t3d_pw::lds_can(const PwCall& c) {
+  return (c.dtype == T3D_F32 || c.dtype == T3D_BF16) && !c.wfrag && (c.op == PW_FWD || c.op == PW_DGRAD);
 }
 
-// include/t3d.h
-extern "C" int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
-                            void* stream);
-extern "C" int t3d_pwconv_fwd_mat(int dtype, const void* y_in, const t3d_prologue* pro_in, const void* residual, void* z_out,
-                                  const void* w, void* y, double* stats, int M, int HW, int K, int N, void* stream) {
-  if (!y_in || !pro_in || !z_out || !w || !y) return T3D_ERR_ARG;
-  if (pro_in->se || M <= 0 || K <= 0 || N <= 0 || (K % 8) || (N % 8) || HW <= 0) return T3D_ERR_ARG;
-  const bool wfrag = (dtype & T3D_W_FRAG) != 0;
-  dtype &= ~T3D_W_FRAG;
-  if (dtype == T3D_BF16) {
-    GemmArgs a{};
-    a.wfrag = wfrag ? 1 : 0;
-    a.a0 = y_in;
-    a.p0 = pro_in->scale; a.p1 = pro_in->shift; a.act = pro_in->act;
-    a.z_res = residual; a.z_out = z_out;
-    a.w = w; a.out = y; a.stats = stats;
-    a.M = M; a.HW = HW; a.Kin = K; a.Nout = N;
-    const int rc = stream_launch(a, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED || wfrag) return rc;
-  }
-  if (wfrag) return T3D_ERR_ARG;
-  if (dtype == T3D_F32 && !getenv("T3D_F32_TILED")) {
-    // fp32 storage: the register-operand kernel materialises the block output itself (pwconv_f32_reg.hip)
-    if (const int rc = t3d_fold_fallback(pro_in->scale, reinterpret_cast<hipStream_t>(stream))) return rc;
-    GemmArgs a{};
-    a.a0 = y_in;
-    a.p0 = pro_in->scale; a.p1 = pro_in->shift; a.act = pro_in->act;
-    a.z_res = residual; a.z_out = z_out;
-    a.w = w; a.out = y; a.stats = stats;
-    a.M = M; a.HW = HW; a.Kin = K; a.Nout = N;
-    const int rc = f32_reg_launch(a, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
-  // no materialising kernel for this case (fp32 training forward, shapes outside the streaming kernel): the two launches it fuses
-  if (const int rc = t3d_bn_apply(dtype, y_in, pro_in, residual, z_out, M, K, stream)) return rc;
-  return t3d_pwconv_fwd(dtype, z_out, nullptr, w, nullptr, y, stats, M, HW, K, N, stream);
+int t3d_pw::lds_launch(const PwCall& c, GemmArgs& a, hipStream_t st) {
+  if (!lds_can(c)) return T3D_ERR_ARG;
+  return c.dtype == T3D_F32 ? launch<float>(a, st) : launch<bf16_t>(a, st);
 }
-
-extern "C" int t3d_pwconv_dgrad(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const void* wt,
-                                const void* x_raw, const t3d_prologue* pro_in, const void* residual, void* dx,
-                                double* stats, float* ps_stats, int M, int HW, int K, int N, void* stream) {
-  if (!dz || !y || !bb || !wt || !dx || !bb->beta) return T3D_ERR_ARG;
-  GemmArgs a{};
-  a.dgrad = 1;
-  a.a0 = dz; a.a1 = y;
-  a.p0 = bb->alpha; a.p1 = bb->beta; a.p2 = bb->gamma; a.per_sample = bb->per_sample;
-  a.w = wt;
-  if (x_raw) {
-    a.e_y = x_raw;
-    if (pro_in) {
-      a.e_scale = pro_in->scale; a.e_shift = pro_in->shift; a.e_se = pro_in->se;
-      a.e_act = pro_in->act; a.e_se_after = pro_in->se_after_act;
-    }
-  }
-  a.e_res = residual; a.out = dx; a.stats = stats; a.ps_stats = ps_stats;
-  a.M = M; a.HW = HW; a.Kin = N; a.Nout = K;  // contraction runs over the forward OUTPUT channels
-  return dispatch(dtype, a, stream);
-}
-

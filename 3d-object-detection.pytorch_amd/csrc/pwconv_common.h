@@ -1,5 +1,5 @@
-// Shared between the two pointwise-conv GEMM kernels (pwconv.hip: LDS-staged, fp32 + bf16;
-// pwconv_stream.hip: barrier-free streaming kernel, bf16).
+// Shared between the pointwise-conv GEMM kernels (pwconv.hip: LDS-staged, fp32 + bf16; pwconv_stream.hip: barrier-free
+// streaming kernel, bf16 / fp16; pwconv_deep.hip; pwconv_f32_reg.hip).  Their launchers: pwconv_route.h.
 #pragma once
 #include "common.h"
 
@@ -50,16 +50,5 @@ template <> __device__ __forceinline__ void stvec<float>(float* p, const float* 
 }
 template <> __device__ __forceinline__ void stvec<bf16_t>(bf16_t* p, const float* v) { Vec8<bf16_t>::store(p, v); }
 
-
-// bf16 streaming kernel (pwconv_stream.hip); returns T3D_ERR_UNSUPPORTED when the shape does not fit it
-int stream_launch(GemmArgs& a, hipStream_t st);
-// bf16 kernel for deep contractions with wide outputs (pwconv_deep.hip: operand staged once, fragment-order weights streamed
-// from L2); returns T3D_ERR_UNSUPPORTED for every other shape.  deep_shape: the shapes it takes (t3d_pwconv_wants_frag)
-int deep_launch(GemmArgs& a, hipStream_t st);
-bool deep_shape(int Kin, int Nout);
-// the same kernel in fp16 storage, inference forward only (pwconv_stream_f16.hip)
-int stream_launch_f16(GemmArgs& a, hipStream_t st);
-// fp32 storage, inference forward of many-pixel layers (pwconv_f32_reg.hip); T3D_ERR_UNSUPPORTED for everything else
-int f32_reg_launch(GemmArgs& a, hipStream_t st);
 
 }  // namespace t3d_pw

@@ -30,7 +30,7 @@
 // No squeeze-excite / per-sample coefficients, no bias, no materialising operand: those shapes stay with the streaming kernel.
 #include <cstdlib>
 #include <type_traits>
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 namespace t3d_pw {
 namespace {
@@ -319,10 +319,12 @@ __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, cons
   DEEP_STAMP(5);
 }
 
+// the operand's double buffer + 3 coefficient rows of the whole contraction + the chunk's sums
+size_t deep_lds(int KS, int ntiles, int KSP = 4) { return (size_t)2 * RT * KSP * 1024 + (size_t)3 * KS * 32 * 4 + (size_t)ntiles * 16 * (2 * 4 + 2 * 8); }
+
 template <bool DG, int NTW, int KSP>
 int launch_deep(GemmArgs& a, int KS, int ntiles, int nchunks, hipStream_t st) {
-  const size_t lds = (size_t)2 * RT * KSP * 1024 + (size_t)3 * KS * 32 * 4 + (size_t)ntiles * 16 * (2 * 4 + 2 * 8);
-  if (lds > 150 * 1024) return T3D_ERR_UNSUPPORTED;
+  const size_t lds = deep_lds(KS, ntiles, KSP);
   const void* fn = (const void*)pw_deep_kernel<DG, NTW, KSP>;
   if (lds > 64 * 1024) (void)t3d_max_lds(fn, (int)lds);
   a.quant = (!DG && a.stats && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for(a.M) : T3dQuant{0.0, 0.0};
@@ -365,19 +367,31 @@ bool deep_shape(int Kin, int Nout) {
   return !(nt_cap >= 2 && Nout <= nt_cap * 16);
 }
 
-// bf16, a.w in fragment order; T3D_ERR_UNSUPPORTED = "not a launch for this kernel"
-int deep_launch(GemmArgs& a, hipStream_t st) {
-  if (a.a2 || a.z_out || a.per_sample || a.ps_stats || a.e_se || a.bias || (!a.dgrad && a.p2)) return T3D_ERR_UNSUPPORTED;
-  if (a.row0 && a.row0 != a.Kin) return T3D_ERR_UNSUPPORTED;
-  if (a.dgrad && (!a.a1 || !a.p0 || !a.p1 || !a.p2)) return T3D_ERR_UNSUPPORTED;
-  if (!deep_shape(a.Kin, a.Nout)) return T3D_ERR_UNSUPPORTED;
-  const int KS = cdiv(a.Kin, 32);
-  const int pairs = cdiv(a.Nout, 32);
-  // a wave's share: 2 tiles x 4 k-steps of weights ahead, chunks of <= 16 tiles = 256 channels, evenly sized (every chunk stages
-  // AND transforms the operand again).  (3 tiles x 2 k-steps in ONE chunk of <= 24 tiles: the two launches it changes get 12 and
-  // 20 us faster alone, the STEP does not -- finding 20's lesson once more; code removed, see git history)
-  const int nchunks = cdiv(pairs, 8), ntiles = 2 * cdiv(pairs, nchunks);
-  return a.dgrad ? launch_deep<true, 2, 4>(a, KS, ntiles, nchunks, st) : launch_deep<false, 2, 4>(a, KS, ntiles, nchunks, st);
+// a wave's share: 2 tiles x 4 k-steps of weights ahead, chunks of <= 16 tiles = 256 channels, evenly sized (every chunk stages
+// AND transforms the operand again).  (3 tiles x 2 k-steps in ONE chunk of <= 24 tiles: the two launches it changes get 12 and
+// 20 us faster alone, the STEP does not -- finding 20's lesson once more; code removed, see git history)
+struct DeepChunks {
+  int nchunks, ntiles;
+  explicit DeepChunks(int Nout) {
+    const int pairs = cdiv(Nout, 32);
+    nchunks = cdiv(pairs, 8);
+    ntiles = 2 * cdiv(pairs, nchunks);
+  }
+};
+
+// bf16 forward / data gradient with `w` in fragment order, shared coefficients, no gates, no bias, deep_shape -- and a contraction
+// whose coefficient rows leave the operand buffers room in 150 KB of LDS (Kin <= 9536 at 16 tiles per chunk)
+bool deep_can(const PwCall& c) {
+  if (c.dtype != T3D_BF16 || !c.wfrag || (c.op != PW_FWD && c.op != PW_DGRAD) || c.gen() || c.bias) return false;
+  if (c.op == PW_DGRAD && !c.alpha_gamma) return false;
+  return deep_shape(c.Kin, c.Nout) && deep_lds(cdiv(c.Kin, 32), DeepChunks(c.Nout).ntiles) <= 150 * 1024;
+}
+
+int deep_launch(const PwCall& c, GemmArgs& a, hipStream_t st) {
+  if (!deep_can(c)) return T3D_ERR_ARG;
+  const DeepChunks ch(a.Nout);
+  return a.dgrad ? launch_deep<true, 2, 4>(a, cdiv(a.Kin, 32), ch.ntiles, ch.nchunks, st)
+                 : launch_deep<false, 2, 4>(a, cdiv(a.Kin, 32), ch.ntiles, ch.nchunks, st);
 }
 
 }  // namespace t3d_pw

@@ -19,7 +19,7 @@
 // form (the bf16 kernel's structure, pwconv_stream.hip) was built first and measured slower on 18 of MobileNetV2's 19 layer
 // shapes (3.5 against 2.6 ms per batch-256 forward; DESIGN.md finding 47).  No squeeze-excite gate, no statistics, no data
 // gradient: those stay with pwconv.hip (the training forward / backward of the parity mode, MobileNetV3's gated layers).
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 #include <cstdlib>
 
 namespace t3d_pw {
@@ -231,22 +231,40 @@ __global__ __launch_bounds__(256) void pw_f32_reg_kernel(const GemmArgs a, const
   }
 }
 
+// Task shape (round-5 sweep): output tiles per wave = the count that pads the layer's tiles least, 5 and 4 before 6 (4 x 6 takes
+// 224 registers) before 3; 4 pixel groups per wave unless that leaves fewer than 128 workgroups (7x7 x 256 = 784 groups x 10
+// tiles as 4 x 5 would be 98), then 2
+struct RegTask {
+  int R, NT, nchunks;
+  long long grid;
+  explicit RegTask(const PwCall& c) {
+    const int tiles = cdiv(c.Nout, 16), G = cdiv(c.M, 16);
+    const bool dgrad = c.op == PW_DGRAD;
+    NT = 2;
+    if (tiles > 2) {
+      int pad = 1 << 30;
+      for (int n : {5, 4, 6, 3})
+        if (cdiv(tiles, n) * n < pad) { pad = cdiv(tiles, n) * n; NT = n; }
+    }
+    nchunks = cdiv(tiles, NT);
+    R = (long long)cdiv(cdiv(G, 4), 4) * nchunks >= 128 ? 4 : 2;
+    // 4 x 5 / 4 x 6 run out of registers with three operand streams (data gradient: 308 / 364), with the sums' epilogue at 4 x 6
+    // or beside a residual (260), and with gates (one more float4 per pixel row and step)
+    if (R == 4 && NT > 4 && (dgrad || (c.stats && (NT == 6 || c.residual)) || c.gated)) R = 2;
+    const int npb4 = cdiv(cdiv(G, R), 4);                      // workgroups along the pixels: 4 waves, R pixel groups each
+    long long npw = (long long)cdiv(npb4, 8) * 8;
+    if (c.stats || dgrad) {                                    // persistent: two workgroups per CU, whole XCD lanes
+      const long long cap = (512 / nchunks) / 8 * 8;
+      if (npw > (cap < 8 ? 8 : cap)) npw = cap < 8 ? 8 : cap;
+    }
+    grid = npw * nchunks;
+  }
+};
+
 template <int R, int NT>
-int launch_reg(GemmArgs& a, hipStream_t st) {
-  const int KG = cdiv(a.Kin, 16), nchunks = cdiv(cdiv(a.Nout, 16), NT);
-  const int npb4 = cdiv(cdiv(cdiv(a.M, 16), R), 4);          // workgroups along the pixels: 4 waves, R pixel groups each
-  long long npw = (long long)cdiv(npb4, 8) * 8;
-  if constexpr (R == 4 && NT > 4) {
-    if (a.dgrad) return launch_reg<2, NT>(a, st);            // (three operand streams: 308 / 364 registers at 4 x 5 / 4 x 6)
-    if (a.stats && (NT == 6 || a.z_res)) return launch_reg<2, NT>(a, st); // (260 registers with the sums' epilogue at 4 x 6)
-    if (a.p2 && !a.dgrad) return launch_reg<2, NT>(a, st);                // (gates: one more float4 per pixel row and step)
-  }
-  if (a.stats || a.dgrad) {                                  // persistent: two workgroups per CU, whole XCD lanes
-    const long long cap = (512 / nchunks) / 8 * 8;
-    if (npw > (cap < 8 ? 8 : cap)) npw = cap < 8 ? 8 : cap;
-  }
-  const long long grid = npw * nchunks;
-  if (grid >= (1ll << 31)) return T3D_ERR_UNSUPPORTED;
+int launch_reg(GemmArgs& a, const RegTask& t, hipStream_t st) {
+  const int KG = cdiv(a.Kin, 16), nchunks = t.nchunks;
+  const long long grid = t.grid;
   const size_t lds = (size_t)3 * KG * 16 * 4 + (size_t)NT * 32 * 8;
   const int nrep = g_t3d_reduce.nrep > 0 ? g_t3d_reduce.nrep : 1;
   const long long rstride = g_t3d_reduce.stats_stride;
@@ -276,42 +294,35 @@ int launch_reg(GemmArgs& a, hipStream_t st) {
 }
 
 template <int R>
-int launch_reg_nt(GemmArgs& a, int NT, hipStream_t st) {
-  switch (NT) {
-    case 2: return launch_reg<R, 2>(a, st);
-    case 3: return launch_reg<R, 3>(a, st);
-    case 4: return launch_reg<R, 4>(a, st);
-    case 5: return launch_reg<R, 5>(a, st);
-    default: return launch_reg<R, 6>(a, st);
+int launch_reg_nt(GemmArgs& a, const RegTask& t, hipStream_t st) {
+  switch (t.NT) {
+    case 2: return launch_reg<R, 2>(a, t, st);
+    case 3: return launch_reg<R, 3>(a, t, st);
+    case 4: return launch_reg<R, 4>(a, t, st);
+    case 5: return launch_reg<R, 5>(a, t, st);
+    default: return launch_reg<R, 6>(a, t, st);
   }
 }
 
 }  // namespace
 
-// fp32 storage, inference forward; T3D_ERR_UNSUPPORTED = "not a launch for this kernel" (pwconv.hip takes it)
-int f32_reg_launch(GemmArgs& a, hipStream_t st) {
-  if (a.dgrad) {
-    if (!a.a1 || !a.p0 || !a.p1 || !a.p2 || a.per_sample || a.ps_stats || a.e_se || a.a2 || a.fold || a.kz > 1 ||
-        a.wfrag || a.bias || a.z_out || a.z_res || !a.out)
-      return T3D_ERR_UNSUPPORTED;
-  } else
-  if (a.ps_stats || (a.p2 && a.z_out) || a.a1 || a.a2 || a.fold || a.per_sample || a.e_se || a.kz > 1 ||
-      a.wfrag || (a.z_res && !a.z_out) || (a.z_out && (a.act != T3D_ACT_NONE || a.bias)) ||
-      (a.stats && !a.out))
-    return T3D_ERR_UNSUPPORTED;
-  if ((a.Kin % 8) || (a.Nout % 8) || a.M < 1024) return T3D_ERR_UNSUPPORTED;      // (few-pixel layers: the split-contraction path)
-  // Task shape (round-5 sweep): output tiles per wave = the count that pads the layer's tiles least, 5 and 4
-  // before 6 (4 x 6 takes 224 registers) before 3; 4 pixel groups per wave unless that leaves fewer than 128 workgroups (7x7 x
-  // 256 = 784 groups x 10 tiles as 4 x 5 would be 98), then 2
-  const int tiles = cdiv(a.Nout, 16), G = cdiv(a.M, 16);
-  int NT = 2;
-  if (tiles > 2) {
-    int pad = 1 << 30;
-    for (int c : {5, 4, 6, 3})
-      if (cdiv(tiles, c) * c < pad) { pad = cdiv(tiles, c) * c; NT = c; }
+// fp32 storage, many-pixel layers (few-pixel ones: the LDS-tiled kernel's split contraction): forward with any prologue and a
+// bias, materialising forward of a linear block output, data gradient with shared coefficients and no gates
+bool reg32_can(const PwCall& c) {
+  if (c.dtype != T3D_F32 || c.wfrag || c.M < 1024) return false;
+  switch (c.op) {
+    case PW_FWD: break;
+    case PW_MAT: if (c.gated || c.act != T3D_ACT_NONE || c.bias) return false; break;
+    case PW_DGRAD: if (!c.alpha_gamma || c.per_sample || c.ps_stats || c.e_se) return false; break;
+    default: return false;
   }
-  const int R = (long long)cdiv(cdiv(G, 4), 4) * cdiv(tiles, NT) >= 128 ? 4 : 2;
-  return R == 4 ? launch_reg_nt<4>(a, NT, st) : launch_reg_nt<2>(a, NT, st);
+  return RegTask(c).grid < (1ll << 31);
+}
+
+int reg32_launch(const PwCall& c, GemmArgs& a, hipStream_t st) {
+  if (!reg32_can(c)) return T3D_ERR_ARG;
+  const RegTask t(c);
+  return t.R == 4 ? launch_reg_nt<4>(a, t, st) : launch_reg_nt<2>(a, t, st);
 }
 
 }  // namespace t3d_pw

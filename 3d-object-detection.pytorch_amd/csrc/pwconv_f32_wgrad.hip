@@ -15,7 +15,7 @@
 // (t3d_pw_wgrad_reduce): bit-reproducible.  Blocks past the matrix edge (N or K not a multiple of 64) load clamped addresses
 // and multiply by zero coefficients.  No squeeze-excite gates, no per-sample coefficients: those stay with pwconv_wgrad.hip.
 #include <cstdlib>
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 namespace {
 
@@ -105,10 +105,41 @@ __global__ __launch_bounds__(256) void pw_wgrad_f32_reg_kernel(const Wg32Args a)
 
 int t3d_pw_wgrad_reduce(const float* ws, float* dw, int N, int K, int PB, int QB, int qtiles, int tiles, int S, hipStream_t st);
 
-// fp32 storage, per-channel coefficients, no gates; T3D_ERR_UNSUPPORTED = "not a launch for this kernel" (pwconv_wgrad.hip takes it)
-int t3d_pw_wgrad_f32_reg(const float* dz, const float* y, const t3d_bnbwd* bb, const float* x, const t3d_prologue* pro, float* dw,
-                         int M, int K, int N, hipStream_t st) {
-  if (bb->per_sample || (pro && pro->se) || M < 1024 || !bb->alpha || !bb->gamma) return T3D_ERR_UNSUPPORTED;
+namespace t3d_pw {
+
+// pixel splits: whole rounds of workgroups -- 256 k workgroups of four splits each over the (tn tk) blocks, the largest k <= 3 that
+// leaves a split >= 512 pixels (128 steps); measured per layer (tools/time_pw_f32_bwd.py): 28x28 x 256, 3 blocks: 392 splits
+// = 294 workgroups 97 us, 340 splits = 255 workgroups 67 us; <= 48 MB of partial tiles
+struct Wg32Splits {
+  int tn, tk, rows_per_split, S, SG;   // SG: workgroups along the pixels (4 splits each)
+  Wg32Splits(int M, int K, int N) : tn(cdiv(N, 64)), tk(cdiv(K, 64)) {
+    int SGsel = 0;
+    for (int k = 3; k >= 1 && !SGsel; --k) {
+      const int sg = (256 * k) / (tn * tk);
+      if (sg >= 1 && (M / (4 * sg) >= 512 || k == 1)) SGsel = sg;
+    }
+    S = 4 * (SGsel > 0 ? SGsel : 1);
+    const int maxs = cdiv(M, 512);
+    if (S > maxs) S = maxs;
+    if (S < 4) S = 4;
+    S = (S + 3) & ~3;
+    rows_per_split = cdiv(cdiv(M, S), 4 * DEPTH) * 4 * DEPTH;
+    S = cdiv(M, rows_per_split);
+    SG = cdiv(S, 4);
+  }
+  size_t bytes() const { return (size_t)SG * 4 * tn * tk * 64 * 64 * sizeof(float); }   // the partial tiles
+};
+
+// fp32 storage, per-channel coefficients, no gates, many pixels, and a workspace (t3d_set_workspace) that holds the partial tiles
+bool reg32_wgrad_can(const PwCall& c) {
+  if (c.dtype != T3D_F32 || c.op != PW_WGRAD || c.per_sample || c.gated || c.M < 1024 || !c.alpha_gamma) return false;
+  return g_t3d_ws.ptr && (size_t)g_t3d_ws.bytes >= Wg32Splits(c.M, c.Nout, c.Kin).bytes();
+}
+
+int reg32_wgrad_launch(const PwCall& c, const float* dz, const float* y, const t3d_bnbwd* bb, const float* x, const t3d_prologue* pro,
+                       float* dw, hipStream_t st) {
+  if (!reg32_wgrad_can(c)) return T3D_ERR_ARG;
+  const int M = c.M, K = c.Nout, N = c.Kin;   // (the contraction runs over the pixels; PwCall names the sides as the data gradient does)
   Wg32Args a{};
   a.dz = dz; a.y = y; a.x = x;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma;
@@ -118,26 +149,10 @@ int t3d_pw_wgrad_f32_reg(const float* dz, const float* y, const t3d_bnbwd* bb, c
   a.lo = (act == T3D_ACT_RELU || act == T3D_ACT_RELU6) ? 0.f : -inf;
   a.hi = act == T3D_ACT_RELU6 ? 6.f : inf;
   a.M = M; a.K = K; a.N = N;
-  const int tn = cdiv(N, 64), tk = cdiv(K, 64);
+  const Wg32Splits sp(M, K, N);
+  const int tn = sp.tn, tk = sp.tk, S = sp.S, SG = sp.SG;
   a.tk = tk;
-  // pixel splits: whole rounds of workgroups -- 256 k workgroups of four splits each over the (tn tk) blocks, the largest k <= 3 that
-  // leaves a split >= 512 pixels (128 steps); measured per layer (tools/time_pw_f32_bwd.py): 28x28 x 256, 3 blocks: 392 splits
-  // = 294 workgroups 97 us, 340 splits = 255 workgroups 67 us; <= 48 MB of partial tiles
-  int SGsel = 0;
-  for (int k = 3; k >= 1 && !SGsel; --k) {
-    const int sg = (256 * k) / (tn * tk);
-    if (sg >= 1 && (M / (4 * sg) >= 512 || k == 1)) SGsel = sg;
-  }
-  int S = 4 * (SGsel > 0 ? SGsel : 1);
-  const int maxs = cdiv(M, 512);
-  if (S > maxs) S = maxs;
-  if (S < 4) S = 4;
-  S = (S + 3) & ~3;
-  a.rows_per_split = cdiv(cdiv(M, S), 4 * DEPTH) * 4 * DEPTH;
-  S = cdiv(M, a.rows_per_split);
-  const int SG = cdiv(S, 4);                                     // workgroups along the pixels (4 splits each)
-  const size_t need = (size_t)SG * 4 * tn * tk * 64 * 64 * sizeof(float);
-  if (!g_t3d_ws.ptr || (size_t)g_t3d_ws.bytes < need) return T3D_ERR_UNSUPPORTED;
+  a.rows_per_split = sp.rows_per_split;
   a.ws = reinterpret_cast<float*>(g_t3d_ws.ptr);
   // (splits past S inside the last workgroup return at once: their tiles must read as zeros)
   if (SG * 4 != S && hipMemsetAsync(a.ws + (size_t)S * tn * tk * 4096, 0, (size_t)(SG * 4 - S) * tn * tk * 4096 * sizeof(float), st) != hipSuccess)
@@ -149,3 +164,5 @@ int t3d_pw_wgrad_f32_reg(const float* dz, const float* y, const t3d_bnbwd* bb, c
   T3D_CHECK_LAUNCH();
   return t3d_pw_wgrad_reduce(a.ws, dw, N, K, 64, 64, tk, tn * tk, SG * 4, st);
 }
+
+}  // namespace t3d_pw

@@ -20,7 +20,7 @@
 // flight), not by a block-wide pipeline.
 #include <cstdlib>
 #include <type_traits>
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 // Storage type of this translation unit.  The file is compiled twice: as it stands for bf16 (training + inference, every
 // variant), and through pwconv_stream_f16.hip for fp16 INFERENCE (forward variants only): three more mantissa bits at every
@@ -30,11 +30,13 @@ typedef bf16_t ST;
 typedef bf16x8 ST8;
 #define T3D_PW_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define T3D_PW_LAUNCH stream_launch
+#define T3D_PW_CAN stream_can
 #else
 typedef f16_t ST;
 typedef f16x8 ST8;
 #define T3D_PW_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define T3D_PW_LAUNCH stream_launch_f16
+#define T3D_PW_CAN stream_f16_can
 #endif
 
 namespace t3d_pw {
@@ -576,8 +578,9 @@ template <int NT, int R, bool DG, bool GEN, bool YF = false, int KU = 2, bool ZM
 int launch_v(GemmArgs& a, int KS, hipStream_t st) {
   constexpr int BN = NT * 16;
   const int kpad = KS * 32;
+  // (<= 147.5 KB: the chunk choice below keeps NT * KS <= 120 and KS <= 60, so 120 KB of weights + 60 * 384 B of coefficients +
+  // 160 * 32 B of sums)
   const size_t lds = (size_t)NT * KS * 1024 + (size_t)3 * kpad * 4 + BN * 4 * 4 + BN * 2 * 8;
-  if (lds > 150 * 1024) return T3D_ERR_UNSUPPORTED;
   const int nchunks = cdiv(a.Nout, BN);
   const int ngroups = cdiv(a.M, 16 * R);
   // small weight chunks: 4-wave blocks, as many per CU as registers / LDS admit (each wave hides its own
@@ -607,15 +610,10 @@ int launch_v(GemmArgs& a, int KS, hipStream_t st) {
     const int up = (nxb + 7) & ~7;            // round up while the launch still fits the chip in one wave of blocks
     nxb = (up * nchunks <= 256 * per_cu) ? up : (nxb & ~7);
   }
-  // a pending BatchNorm-finalize request belongs to this launch when it names the coefficients of its operand
-  // (per-sample coefficients and the y-free variant have none to derive)
   a.quant = (!DG && a.stats && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for(a.M) : T3dQuant{0.0, 0.0};
-  if (YF || a.per_sample) {
-    if (const int rc = t3d_fold_fallback(a.p0, st)) return rc;
-    a.fold = nullptr;
-  } else {
-    a.fold = t3d_take_fold(a.p0);
-  }
+  // a pending BatchNorm-finalize request belongs to this launch when it names the coefficients of its operand
+  // (per-sample coefficients and the y-free variant have none to derive: pwconv_route.hip has the rule)
+  a.fold = (YF || a.per_sample) ? nullptr : t3d_take_fold(a.p0);
   T3D_LAUNCH_TIMED((pw_stream_kernel<NT, R, DG, GEN, YF, KU, ZM>), dim3(nxb * nchunks), dim3(threads), lds, st, a, nchunks, KS,
                      g_t3d_reduce.nrep, g_t3d_reduce.stats_stride);
   T3D_CHECK_LAUNCH();
@@ -623,11 +621,10 @@ int launch_v(GemmArgs& a, int KS, hipStream_t st) {
 }
 
 template <int NT, int R>
-int launch_nt(GemmArgs& a, int KS, hipStream_t st, int deep_ku = 0) {
+int launch_nt(GemmArgs& a, int KS, hipStream_t st) {
 #ifdef T3D_PW_F16
   // fp16 storage: the inference forward only (BatchNorm + activation prologue, optionally the squeeze-excite gate of the MobileNetV3
-  // layouts on the operand; no materialising operand, no statistics)
-  if (a.a2 || a.dgrad || a.z_out || a.per_sample || a.ps_stats || a.e_se || a.stats) return T3D_ERR_UNSUPPORTED;
+  // layouts on the operand; no materialising operand, no statistics: stream_f16_can)
   if (a.p2) return launch_v<NT, R, false, true>(a, KS, st);
   return launch_v<NT, R, false, false>(a, KS, st);
 #else
@@ -638,10 +635,8 @@ int launch_nt(GemmArgs& a, int KS, hipStream_t st, int deep_ku = 0) {
   // timeline (tools/pw_trace.sh) shows why: per round the operand transform (unpack, BatchNorm affine, activation, pack: ~4.5
   // VALU ops per element, redone per output chunk) costs as much as the load latency, and with 2 waves per SIMD the two do
   // not overlap; staging 120 KB of weights (5.7 us) and the statistics tail (3 us) are the rest.)
-  if (a.dgrad && !gen && deep_ku == 3) return launch_v<NT, R, true, false, false, 3>(a, KS, st);
-  if (a.dgrad && !gen && deep_ku == 5) return launch_v<NT, R, true, false, false, 5>(a, KS, st);
   if (a.dgrad) return gen ? launch_v<NT, R, true, true>(a, KS, st) : launch_v<NT, R, true, false>(a, KS, st);
-  if (a.z_out) return gen ? T3D_ERR_UNSUPPORTED : launch_v<NT, R, false, false, false, 2, true>(a, KS, st);
+  if (a.z_out) return launch_v<NT, R, false, false, false, 2, true>(a, KS, st);   // (never gated: stream_can)
   return gen ? launch_v<NT, R, false, true>(a, KS, st) : launch_v<NT, R, false, false>(a, KS, st);
 #endif
 }
@@ -654,35 +649,35 @@ extern "C" int t3d_debug_pw_trace(unsigned long long* out) {
 }
 #endif
 
-int T3D_PW_LAUNCH(GemmArgs& a, hipStream_t st) {
-  if (!a.row0) a.row0 = a.Kin;
+// what the kernels of this unit take.  Kin <= 1920: a weight chunk of at least two 16-channel tiles has to fit 120 KB of LDS,
+// 120 / ceil(Kin / 32) >= 2 (the y-free data gradient asks with its padded two-segment contraction)
+#ifdef T3D_PW_F16
+bool T3D_PW_CAN(const PwCall& c) { return c.dtype == T3D_F16 && c.op == PW_FWD && !c.stats && c.Kin <= 1920; }
+#else
+bool T3D_PW_CAN(const PwCall& c) {
+  if (c.dtype != T3D_BF16 || c.op == PW_WGRAD || c.Kin > 1920) return false;
+  if (c.ps_stats && (c.stats || c.M % c.HW)) return false;   // the block-level per-sample reduction uses the statistics scratch
+  return !(c.op == PW_MAT && c.gated);                       // no squeeze-excite variant of the materialising operand
+}
+#endif
 
-  if (a.ps_stats && (a.stats || a.M % a.HW)) return T3D_ERR_UNSUPPORTED;   // the block-level per-sample reduction uses the statistics scratch
+int T3D_PW_LAUNCH(const PwCall& c, GemmArgs& a, hipStream_t st) {
+  if (!T3D_PW_CAN(c)) return T3D_ERR_ARG;
+  if (!a.row0) a.row0 = a.Kin;
   const int KS = cdiv(a.Kin, 32);
   // widest chunk whose weights fit ~120 KB of LDS, at most 10 tiles (register budget: 8*NT stat + 4*NT*R acc)
   int nt_cap = (120 * 1024 / 1024) / KS;
   if (nt_cap > 10) nt_cap = 10;
-  // narrow contraction (K <= 64): re-reading the activation per output chunk costs almost nothing, so trade chunks for
-  // registers / occupancy
-  const int small_k_cap = 10;
-  if (a.Kin <= 64 && nt_cap > small_k_cap) nt_cap = small_k_cap;
   // squeeze-excite data gradient (per-sample sums / gates in registers): wider tiles spill (NT = 8: 216 B, 10: 412 B)
   const int gen_cap = 6;
   if (a.dgrad && (a.per_sample || a.ps_stats || a.e_se) && nt_cap > gen_cap) nt_cap = gen_cap;
-  // small-stage data gradients of the projection convs (contraction over 96 / 160 / 320 bottleneck channels, <= 28x28
-  // pixels): all k-steps of a round in flight + hoisted epilogue loads (kernel: HOIST), at a tile width that leaves the
-  // registers for it.  OPT-IN (T3D_PW_DEEP_DG=1): the launches themselves get 3-8 % faster alone (576 <- 96 @14x14: 46.2 ->
-  // 45.0 us, 960 <- 160 @7x7: 31.7 -> 29.1), but the STEP gets slower (8.46 -> 8.54 ms, three A/B pairs): it is bound by the
-  // two streams' combined HBM traffic, and what these launches stop waiting for, the depthwise backward beside them loses
-  const int deep_dg = 0;
-  int deep_ku = 0;
-  if (deep_dg && a.dgrad && !a.a2 && !(a.per_sample || a.ps_stats || a.e_se) && a.e_y && !a.e_res && a.M <= 256 * 28 * 28 &&
-      (KS == 3 || KS % 5 == 0) && a.Nout >= 96) {
-    deep_ku = KS == 3 ? 3 : 5;
-    if (nt_cap > 6) nt_cap = 6;
-  }
-  nt_cap &= ~1;
-  if (nt_cap < 2) return T3D_ERR_UNSUPPORTED;
+  // (small-stage data gradients of the projection convs -- contraction over 96 / 160 / 320 bottleneck channels, <= 28x28 pixels
+  // -- with all k-steps of a round in flight and hoisted epilogue loads, KU = 3 / 5 at NT <= 6, were measured and are not built:
+  // the launches themselves got 3-8 % faster alone (576 <- 96 @14x14: 46.2 -> 45.0 us, 960 <- 160 @7x7: 31.7 -> 29.1), but the
+  // STEP got slower (8.46 -> 8.54 ms, three A/B pairs): it is bound by the two streams' combined HBM traffic, and what these
+  // launches stop waiting for, the depthwise backward beside them loses.  The kernel keeps its KU parameter and HOIST branch:
+  // taking them out would rename every instantiation.)
+  nt_cap &= ~1;   // (>= 2: Kin <= 1920)
   int NT = 2;
   {
     // fewest chunks first, then least padding
@@ -699,16 +694,16 @@ int T3D_PW_LAUNCH(GemmArgs& a, hipStream_t st) {
       !(a.per_sample || a.ps_stats || a.e_se || (!a.dgrad && a.p2)))
     NT = 6;
   switch (NT) {
-    case 2: return launch_nt<2, 2>(a, KS, st, deep_ku);
-    case 4: return launch_nt<4, 2>(a, KS, st, deep_ku);     // (R = 4 for NT = 2 / 4: 5-40 % slower, measured)
+    case 2: return launch_nt<2, 2>(a, KS, st);
+    case 4: return launch_nt<4, 2>(a, KS, st);     // (R = 4 for NT = 2 / 4: 5-40 % slower, measured)
     case 6:
       // two 16-pixel groups per iteration (round 4): twice the loads in flight per wave and two MFMAs per weight fragment read --
       // 16 -> 96 @112x112 216 -> 209 us, 96 <- 24 390 -> 366, 576 -> 96 @14x14 30.0 -> 26.7, step 6.997 -> 6.904 ms (three A/B
       // pairs).  Not for the squeeze-excite / per-sample variants: their extra registers spill at R = 2 (72 VGPRs to scratch)
-      if (a.per_sample || a.ps_stats || a.e_se || (!a.dgrad && a.p2)) return launch_nt<6, 1>(a, KS, st, deep_ku);
-      return launch_nt<6, 2>(a, KS, st, deep_ku);
-    case 8: return launch_nt<8, 1>(a, KS, st, deep_ku);     // (R = 2: forward 64 -> 384 @14x14 -8 %, data gradient spills 32 VGPRs)
-    default: return launch_nt<10, 1>(a, KS, st, deep_ku);
+      if (a.per_sample || a.ps_stats || a.e_se || (!a.dgrad && a.p2)) return launch_nt<6, 1>(a, KS, st);
+      return launch_nt<6, 2>(a, KS, st);
+    case 8: return launch_nt<8, 1>(a, KS, st);     // (R = 2: forward 64 -> 384 @14x14 -8 %, data gradient spills 32 VGPRs)
+    default: return launch_nt<10, 1>(a, KS, st);
   }
 }
 

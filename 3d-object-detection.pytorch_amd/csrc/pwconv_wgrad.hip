@@ -12,7 +12,7 @@
 // range and leaves with fp32 atomics into the fp32 gradient buffer (the reference's [N,K,1,1]).
 #include <cstdlib>
 #include <type_traits>
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 namespace {
 
@@ -191,31 +191,21 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(const WgArgs a) {
 
 }  // namespace
 
-int t3d_pw_wgrad_tr_entry(const void* dz, const void* y, const t3d_bnbwd* bb, const void* x, const t3d_prologue* pro,
-                          float* dw, int M, int HW, int K, int N, hipStream_t st);   // pwconv_wgrad_tr.hip (bf16)
-int t3d_pw_wgrad_f32_reg(const float* dz, const float* y, const t3d_bnbwd* bb, const float* x, const t3d_prologue* pro, float* dw,
-                         int M, int K, int N, hipStream_t st);                       // pwconv_f32_wgrad.hip (fp32)
 // fixed-order sum of partial tiles ws [S][tiles][PB][QB] into dw [N][K] (pwconv_wgrad_tr.hip)
 int t3d_pw_wgrad_reduce(const float* ws, float* dw, int N, int K, int PB, int QB, int qtiles, int tiles, int S, hipStream_t st);
 
-extern "C" int t3d_pwconv_wgrad(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const void* x,
-                                const t3d_prologue* pro, float* dw, int M, int HW, int K, int N, void* stream) {
-  if (!dz || !y || !bb || !x || !dw || M <= 0 || K <= 0 || N <= 0 || (K % 8) || (N % 8) || HW <= 0) return T3D_ERR_ARG;
-  if (dtype == T3D_BF16)
-    return t3d_pw_wgrad_tr_entry(dz, y, bb, x, pro, dw, M, HW, K, N, reinterpret_cast<hipStream_t>(stream));
-  // the kernels below read finished coefficients: a pending derive request for them becomes a launch of its own
-  if (const int rc = t3d_fold_fallback(bb->alpha, reinterpret_cast<hipStream_t>(stream))) return rc;
-  if (dtype == T3D_F32 && !getenv("T3D_F32_TILED")) {
-    // fp32 storage: the register-operand kernel (pwconv_f32_wgrad.hip) where it takes the launch
-    const int rc = t3d_pw_wgrad_f32_reg(reinterpret_cast<const float*>(dz), reinterpret_cast<const float*>(y), bb,
-                                        reinterpret_cast<const float*>(x), pro, dw, M, K, N, reinterpret_cast<hipStream_t>(stream));
-    if (rc != T3D_ERR_UNSUPPORTED) return rc;
-  }
+// fp32 storage only (the kernel's bf16 variant is not built: pwconv_wgrad_tr.hip takes every bf16 call)
+bool t3d_pw::lds_wgrad_can(const PwCall& c) { return c.dtype == T3D_F32 && c.op == PW_WGRAD; }
+
+int t3d_pw::lds_wgrad_launch(const PwCall& c, const void* dz, const void* y, const t3d_bnbwd* bb, const void* x, const t3d_prologue* pro,
+                             float* dw, hipStream_t st) {
+  if (!lds_wgrad_can(c)) return T3D_ERR_ARG;
+  const int M = c.M, K = c.Nout, N = c.Kin;
   WgArgs a{};
   a.dz = dz; a.y = y; a.x = x;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.se = pro->se; a.act = pro->act; a.se_after = pro->se_after_act; }
-  a.dw = dw; a.M = M; a.HW = HW; a.K = K; a.N = N;
+  a.dw = dw; a.M = M; a.HW = c.HW; a.K = K; a.N = N;
   const int tn = cdiv(N, TN), tk = cdiv(K, TK);
   int S = 1024 / (tn * tk);
   const int maxs = cdiv(M, BMK * 2);
@@ -223,15 +213,12 @@ extern "C" int t3d_pwconv_wgrad(int dtype, const void* dz, const void* y, const 
   if (S < 1) S = 1;
   a.rows_per_split = cdiv(cdiv(M, S), BMK) * BMK;
   S = cdiv(M, a.rows_per_split);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // with a workspace (t3d_set_workspace) the pixel splits leave as plain stores and are added in a fixed order:
   // bit-reproducible weight gradients in the parity mode too
   const size_t need = (size_t)S * tn * tk * TN * TK * sizeof(float);
   a.ws = (S > 1 && g_t3d_ws.ptr && (size_t)g_t3d_ws.bytes >= need) ? reinterpret_cast<float*>(g_t3d_ws.ptr) : nullptr;
-  if (dtype != T3D_F32) return T3D_ERR_ARG;
   T3D_LAUNCH_TIMED(pw_wgrad_kernel<float>, dim3(tn, tk, S), dim3(256), 0, st, a);
   T3D_CHECK_LAUNCH();
   if (a.ws) return t3d_pw_wgrad_reduce(a.ws, dw, N, K, TN, TK, tk, tn * tk, S, st);
   return T3D_OK;
 }
-

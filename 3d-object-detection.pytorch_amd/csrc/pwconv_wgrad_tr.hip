@@ -20,7 +20,7 @@
 // Grid = (P tiles * Q tiles) x pixel splits; partial dW leave as fp32 atomics (few, large, spread over the
 // whole dW -- no contention problem here, unlike per-channel sums).
 #include <cstdlib>
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 namespace {
 
@@ -763,18 +763,19 @@ int launch_d(WgtArgs& a, hipStream_t st) {
 
 template <int NTPW, int NTQ, bool SWAP>
 int launch_sw(WgtArgs& a, hipStream_t st) {
-  const int depth = 2;   // 2 measured best (1: -12 %, 3: -2 %)
+  // pixels per step (see the kernel): 64-pixel steps (SK = 2) for the narrow tiles of the layers with many pixels per workgroup
+  // (isolated, B = 256: 112x112 32 -> 16: 181 -> 141 us, 32 -> 32: 174 -> 138 us; the 56x56 / 28x28 layers do not move or lose).
+  // (128-pixel steps, SK = 4, for tiles <= 128 wide were never faster and are not built.)
+  constexpr bool narrow = 64 * NTPW + 16 * NTQ <= 288;
+  const bool sk2 = narrow && a.M >= (1 << 20);
   if (a.yfree) {
-    if constexpr (!SWAP) {
-      const int sk_env = 0;
-      constexpr int width = 64 * NTPW + 16 * NTQ;
-      if constexpr (width <= 288) {
-        const int sk = sk_env ? sk_env : (a.M >= (1 << 20) ? 2 : 1);
-        if (sk >= 2) return launch_d<NTPW, NTQ, false, 2, false, true, 2>(a, st);
-      }
+    // (the y-free operand [dz | x | 1] is wider than x: N + K + 8 > K, so choose_and_launch never swaps it)
+    if constexpr (SWAP) return T3D_ERR_ARG;
+    else {
+      if constexpr (narrow)
+        if (sk2) return launch_d<NTPW, NTQ, false, 2, false, true, 2>(a, st);
       return launch_d<NTPW, NTQ, false, 2, false, true>(a, st);
     }
-    else return T3D_ERR_UNSUPPORTED;
   }
   // SE layers: per-sample coefficients / gates.  Gates staged in LDS (round 6): the loads of the step after next in flight, as in the
   // plain kernel (the per-vector global gate reads of round 3 forced depth 1: two exposed round trips per 32-pixel step)
@@ -782,16 +783,9 @@ int launch_sw(WgtArgs& a, hipStream_t st) {
   // the compiler drain ALL outstanding loads, the next steps' operands included: 2x the plain kernel's duration, isolated)
   if (a.per_sample) return launch_d<NTPW, NTQ, SWAP, 1, 1>(a, st);
   if (a.se) return launch_d<NTPW, NTQ, SWAP, 2, 2>(a, st);
-  if (depth == 1) return launch_d<NTPW, NTQ, SWAP, 1, false>(a, st);
-  // pixels per step (see the kernel): wider steps for the narrow tiles of the layers with many pixels per workgroup
-  const int sk_env = 0;
-  constexpr int width = 64 * NTPW + 16 * NTQ;
-  // (isolated, B = 256: 112x112 32 -> 16: 181 -> 141 us, 32 -> 32: 174 -> 138 us; the 56x56 / 28x28 layers do not move or lose)
-  if constexpr (width <= 288) {
-    const int sk = sk_env ? sk_env : (a.M >= (1 << 20) ? 2 : 1);
-    if (sk >= 4 && width <= 128) return launch_d<NTPW, NTQ, SWAP, 2, false, false, 4>(a, st);
-    if (sk >= 2) return launch_d<NTPW, NTQ, SWAP, 2, false, false, 2>(a, st);
-  }
+  // pipeline depth 2 measured best for the plain kernel (1: -12 %, 3: -2 %)
+  if constexpr (narrow)
+    if (sk2) return launch_d<NTPW, NTQ, SWAP, 2, false, false, 2>(a, st);
   return launch_d<NTPW, NTQ, SWAP, 2, false>(a, st);
 }
 
@@ -799,8 +793,6 @@ template <int NTPW, int NTQ>
 int launch_cfg(WgtArgs& a, hipStream_t st) {
   return a.swap ? launch_sw<NTPW, NTQ, true>(a, st) : launch_sw<NTPW, NTQ, false>(a, st);
 }
-
-
 
 static int choose_and_launch(WgtArgs& a, hipStream_t st) {
   const int M = a.M, K = a.K, N = a.N;
@@ -855,19 +847,18 @@ int t3d_pw_wgrad_reduce(const float* ws, float* dw, int N, int K, int PB, int QB
   return T3D_OK;
 }
 
-// bf16 path of t3d_pwconv_wgrad (pwconv_wgrad.hip keeps the fp32 parity kernel)
-int t3d_pw_wgrad_tr_entry(const void* dz, const void* y, const t3d_bnbwd* bb, const void* x, const t3d_prologue* pro,
-                          float* dw, int M, int HW, int K, int N, hipStream_t st) {
+// bf16 weight gradient: every shape and option of t3d_pwconv_wgrad (pwconv_wgrad.hip keeps the fp32 parity kernel)
+bool t3d_pw::tr_can(const PwCall& c) { return c.dtype == T3D_BF16 && c.op == PW_WGRAD; }
+
+int t3d_pw::tr_launch(const PwCall& c, const void* dz, const void* y, const t3d_bnbwd* bb, const void* x, const t3d_prologue* pro,
+                      float* dw, hipStream_t st) {
+  if (!tr_can(c)) return T3D_ERR_ARG;
   WgtArgs a{};
   a.dz = dz; a.y = y; a.x = x;
   a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.se = pro->se; a.act = pro->act; a.se_after = pro->se_after_act; }
-  a.dw = dw; a.M = M; a.HW = HW; a.K = K; a.N = N;
-  if (a.per_sample) {
-    if (const int rc = t3d_fold_fallback(a.alpha, st)) return rc;
-  } else {
-    a.fold = t3d_take_fold(a.alpha);
-  }
+  a.dw = dw; a.M = c.M; a.HW = c.HW; a.K = c.Nout; a.N = c.Kin;
+  a.fold = a.per_sample ? nullptr : t3d_take_fold(a.alpha);   // (pwconv_route.hip has the rule)
   return choose_and_launch(a, st);
 }
 

@@ -15,7 +15,7 @@
 // 4 to 2 passes over M x N elements (SURVEY.md section 8d counts 4: the figures reported against that budget are
 // therefore "fused" fractions).  Reference semantics: autograd of nn.Conv2d(K, N, 1) + nn.BatchNorm2d(N)
 // (models/mobilenetv3.py:148-149) -- same sums, reassociated.
-#include "pwconv_common.h"
+#include "pwconv_route.h"
 
 int t3d_pw_wgrad_tr_yfree(const void* dz, const void* x, float* tmp, int M, int HW, int K, int N, hipStream_t st);
 // fused y-free backward (pwconv_wgrad_tr.hip)
@@ -217,10 +217,7 @@ static int yfree_prep_impl(const void* wt, const t3d_bnbwd* bb, void* wcat, floa
   if (!w || !bb || !bb->alpha || !bb->beta || !bb->gamma || !wcat || !cvec || K <= 0 || N <= 0 || (K % 8) || (N % 8))
     return T3D_ERR_ARG;
   if (bb->per_sample) return T3D_ERR_UNSUPPORTED;
-  const bool derive = true;
-  const T3dFold* fold = nullptr;
-  if (derive) fold = t3d_take_fold(bb->alpha);
-  else if (const int rc = t3d_fold_fallback(bb->alpha, reinterpret_cast<hipStream_t>(stream))) return rc;
+  const T3dFold* fold = t3d_take_fold(bb->alpha);   // a pending finalize of these coefficients is derived in the kernel's prologue
   T3D_LAUNCH(yfree_prep_kernel, dim3(rup32(K) / 16, rup32(K) / 16), dim3(256), (size_t)3 * N * sizeof(float),
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const bf16_t*>(w), bb->alpha, bb->beta, bb->gamma,
                      reinterpret_cast<bf16_t*>(wcat), cvec, K, N, rup32(N), rup32(K), fold, reinterpret_cast<bf16_t*>(wd), PBw);
@@ -243,7 +240,12 @@ extern "C" int t3d_pwconv_dgrad_yfree(const void* dz, const void* x, const void*
     if (pro_in) { a.e_scale = pro_in->scale; a.e_shift = pro_in->shift; a.e_act = pro_in->act; }
   }
   a.M = M; a.HW = HW; a.Kin = rup32(N) + rup32(K); a.Nout = K;
-  return t3d_pw::stream_launch(a, reinterpret_cast<hipStream_t>(stream));   // T3D_ERR_UNSUPPORTED if the shape does not fit
+  // the streaming kernel's own limits, asked with the padded two-segment contraction (the caller keeps the two-tensor path)
+  t3d_pw::PwCall c{};
+  c.op = t3d_pw::PW_DGRAD; c.dtype = T3D_BF16; c.bias = 1; c.stats = stats != nullptr; c.alpha_gamma = 1;
+  c.M = M; c.HW = HW; c.Kin = a.Kin; c.Nout = K;
+  if (!t3d_pw::stream_can(c)) return T3D_ERR_UNSUPPORTED;
+  return t3d_pw::stream_launch(c, a, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int t3d_pwconv_wgrad_yfree(const void* dz, const void* x, const t3d_bnbwd* bb, const void* w, float* dw,

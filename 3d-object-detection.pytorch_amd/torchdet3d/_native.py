@@ -16,6 +16,9 @@ W_FRAG = 0x100                  # include/t3d.h: T3D_W_FRAG (weights in fragment
 F32, BF16, F16 = 0, 1, 2        # include/t3d.h: T3D_F32 / T3D_BF16 / T3D_F16 (fp16: inference forward only)
 ACT = {'none': 0, 'relu': 1, 'relu6': 2, 'hswish': 3}
 DW_AUTO, DW_TILE, DW_ROW3, DW_PLANE7, DW_ROWK, DW_LDS = -1, 0, 1, 2, 3, 4      # include/t3d.h: T3D_DW_* (depthwise kernel families)
+# include/t3d.h: T3D_PW_* (pointwise kernel families; PW_PAIR: t3d_pwconv_fwd_mat as t3d_bn_apply + t3d_pwconv_fwd) and T3D_PW_OP_*
+PW_AUTO, PW_DEEP, PW_STREAM, PW_REG32, PW_LDS, PW_TR, PW_PAIR = -1, 0, 1, 2, 3, 4, 5
+PW_OP_FWD, PW_OP_FWD_STATS, PW_OP_MAT, PW_OP_DGRAD, PW_OP_WGRAD = 0, 1, 2, 3, 4
 ERR_ARG, ERR_UNSUPPORTED = -1, -3
 POOL = {'avg': 0, 'max': 1, 'avg+max': 2}
 _P, _I, _F, _D, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
@@ -69,6 +72,8 @@ SIGNATURES = {
     't3d_dwconv_route': [_I] * 10,
     't3d_dwconv_force_route': [_I],
     't3d_pwconv_wgrad': [_I, _P, _P, _BP, _P, _PP, _P, _I, _I, _I, _I, _P],
+    't3d_pwconv_route': [_I] * 15,
+    't3d_pwconv_force_route': [_I],
     't3d_pwconv_yfree_prep': [_P, _BP, _P, _P, _I, _I, _P],
     't3d_pwconv_dgrad_yfree': [_P, _P, _P, _P, _P, _PP, _P, _P, _P, _I, _I, _I, _I, _P],
     't3d_pwconv_wgrad_yfree': [_P, _P, _BP, _P, _P, _I, _I, _I, _I, _P],

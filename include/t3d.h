@@ -139,6 +139,28 @@ int t3d_pack_weight(int dtype, const float* w, void* out, int rows, int cols, in
 int t3d_pwconv_wgrad(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb, const void* x,
                      const t3d_prologue* pro, float* dw, int M, int HW, int K, int N, void* stream);
 
+/* The pointwise entry points (t3d_pwconv_fwd / _fwd_mat / _dgrad / _wgrad) pick ONE kernel family per call, by a pure function of
+ * the call's dtype, options and sizes (csrc/pwconv_route.hip), ahead of every side effect.  Route ids:
+ *   T3D_PW_DEEP    deep contractions with fragment-order weights (csrc/pwconv_deep.hip; bf16, t3d_pwconv_wants_frag's shapes)
+ *   T3D_PW_STREAM  streaming kernel (csrc/pwconv_stream.hip: bf16, K <= 1920; fp16: inference forward)
+ *   T3D_PW_REG32   fp32 register-operand kernels (csrc/pwconv_f32_reg.hip; weight gradient: pwconv_f32_wgrad.hip), M >= 1024
+ *   T3D_PW_LDS     LDS-tiled kernels (csrc/pwconv.hip, pwconv_wgrad.hip): fp32 and bf16, row-major weights
+ *   T3D_PW_TR      bf16 weight gradient (csrc/pwconv_wgrad_tr.hip)
+ *   T3D_PW_PAIR    not a kernel: t3d_pwconv_fwd_mat runs the two calls it fuses, t3d_bn_apply + t3d_pwconv_fwd
+ * t3d_pwconv_route RETURNS the route id of such a call, or the negative T3D_ERR_* the entry point would return; it makes no
+ * device call.  op: T3D_PW_OP_* (FWD_STATS: t3d_pwconv_fwd with y == NULL); dtype may carry T3D_W_FRAG; the flags say what the call
+ * passes: gated = pro->se, per_sample = bb->per_sample, ps_stats / bias / stats / residual = that pointer non-NULL, e_se = x_raw and
+ * pro_in->se, alpha_gamma = bb->alpha and bb->gamma non-NULL, act = the operand's activation; M, HW, K, N as the entry point takes
+ * them.  The fp32 weight gradient also reads the size of the workspace (t3d_set_workspace).
+ * t3d_pwconv_force_route (tests and timing tools only; process-wide, T3D_PW_AUTO clears it): while a family is forced, calls it
+ * can take go to it and every other call returns T3D_ERR_UNSUPPORTED, launching nothing -- except that t3d_pwconv_fwd_mat with
+ * row-major weights answers T3D_PW_PAIR, whose convolution is routed under the same force. */
+enum { T3D_PW_AUTO = -1, T3D_PW_DEEP = 0, T3D_PW_STREAM = 1, T3D_PW_REG32 = 2, T3D_PW_LDS = 3, T3D_PW_TR = 4, T3D_PW_PAIR = 5 };
+enum { T3D_PW_OP_FWD = 0, T3D_PW_OP_FWD_STATS = 1, T3D_PW_OP_MAT = 2, T3D_PW_OP_DGRAD = 3, T3D_PW_OP_WGRAD = 4 };
+int t3d_pwconv_route(int op, int dtype, int gated, int per_sample, int ps_stats, int e_se, int bias, int stats, int alpha_gamma,
+                     int act, int residual, int M, int HW, int K, int N);
+int t3d_pwconv_force_route(int route);
+
 /* "y-free" backward of a pointwise conv whose input x [M,K] is a finished (materialised) bf16 tensor -- the expand
  * layer nn.Conv2d(K, N, 1) + nn.BatchNorm2d(N) of an inverted-residual block (models/mobilenetv3.py:148-149).
  * Because y = x W^T, the BatchNorm-backward affine dy = alpha*dz + beta*y + gamma never needs the wide tensor y:

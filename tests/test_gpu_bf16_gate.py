@@ -370,31 +370,33 @@ def test_bf16_training_tracks_the_fp32_trajectory_at_the_benchmark_shape():
     gts = [torch.rand(B, 9, 2, device='cuda', generator=g) * 0.6 + 0.2 for _ in range(nb + 1)]
     cats = [torch.randint(0, nc, (B,), device='cuda', generator=g) for _ in range(nb + 1)]
     curves, evals = {}, {}
-    import os
+    from torchdet3d import _native as Nt
     for dt in ('f32', 'f32_tiled', 'bf16'):
-        # 'f32_tiled': the same fp32 run with round 1's LDS-tiled 1x1 forward kernel instead of the register-operand one (round 5):
-        # two fp32 trainings that differ ONLY in the order their dot products are summed -- the yardstick for the bf16 run below
-        os.environ.pop('T3D_F32_TILED', None)
-        if dt == 'f32_tiled':
-            os.environ['T3D_F32_TILED'] = '1'
-        cfg = _cfg('mobilenetv2')
-        cfg.model.storage_dtype = dt.split('_')[0]
-        torch.manual_seed(23)
-        m = build_model(cfg).to('cuda')
-        m.net.reset_parameters(seed=23)
-        opt = build_optimizer(cfg, m)
-        lm = LossManager(build_loss(cfg), cfg.loss.coeffs, cfg.loss.alwa)
-        tr = Trainer(m, None, opt, None, lm, None, 1, '', device='cuda', save_chkpt=False)
-        m.train()
-        curves[dt] = [dict(tr.train_step(imgs[i % nb], gts[i % nb], cats[i % nb], i)) for i in range(steps)]
-        m.eval()
-        assert m.net_eval.dtype == torch.float32
-        with torch.no_grad():
-            kp, lg = m(imgs[nb], cats[nb])
+        # 'f32_tiled': the same fp32 run with round 1's LDS-tiled 1x1 kernels instead of the register-operand ones (round 5; forced
+        # route T3D_PW_LDS): two fp32 trainings that differ ONLY in the order their dot products are summed -- the yardstick for the
+        # bf16 run below
+        try:
+            if dt == 'f32_tiled':
+                Nt.call('t3d_pwconv_force_route', Nt.PW_LDS)
+            cfg = _cfg('mobilenetv2')
+            cfg.model.storage_dtype = dt.split('_')[0]
+            torch.manual_seed(23)
+            m = build_model(cfg).to('cuda')
+            m.net.reset_parameters(seed=23)
+            opt = build_optimizer(cfg, m)
+            lm = LossManager(build_loss(cfg), cfg.loss.coeffs, cfg.loss.alwa)
+            tr = Trainer(m, None, opt, None, lm, None, 1, '', device='cuda', save_chkpt=False)
+            m.train()
+            curves[dt] = [dict(tr.train_step(imgs[i % nb], gts[i % nb], cats[i % nb], i)) for i in range(steps)]
+            m.eval()
+            assert m.net_eval.dtype == torch.float32
+            with torch.no_grad():
+                kp, lg = m(imgs[nb], cats[nb])
+        finally:
+            Nt.call('t3d_pwconv_force_route', Nt.PW_AUTO)
         evals[dt] = (kp.clone(), lg.clone())
         del m, opt, tr
         torch.cuda.empty_cache()
-    os.environ.pop('T3D_F32_TILED', None)
     d = [abs(a['loss'] - b['loss']) for a, b in zip(curves['f32'], curves['bf16'])]
     print('loss fp32 ', [round(r['loss'], 4) for r in curves['f32']])
     print('loss bf16 ', [round(r['loss'], 4) for r in curves['bf16']])

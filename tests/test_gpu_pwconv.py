@@ -412,13 +412,12 @@ def test_pwconv_dgrad(B, HW, K, N, dt, mode):
 
 
 # fp32 storage, data gradient of layers with >= 1024 pixels: the register-operand kernel's variant 6 (csrc/pwconv_f32_reg.hip)
-# against round 1's LDS-tiled kernel on the same inputs (T3D_F32_TILED=1) and against fp64 -- values, both BatchNorm-backward
+# against round 1's LDS-tiled kernel on the same inputs (forced route T3D_PW_LDS) and against fp64 -- values, both BatchNorm-backward
 # sums (sum dx, sum dx . x_raw), spread over the reduction replicas, bit-identical from run to run
 @pytest.mark.parametrize('M,K,N', [(4096, 16, 96), (3001, 24, 144), (2048, 144, 24), (1031, 96, 576), (1024, 160, 960),
                                    (1100, 960, 160), (50000, 32, 16), (1111, 40, 240), (2000, 8, 8)])
 @pytest.mark.parametrize('mode', ['input', 'input_res', 'relu6', 'relu6_res', 'none_stats'])
 def test_pwconv_dgrad_f32_register_kernel(M, K, N, mode):
-    import os
     from torchdet3d import _native as Nt
     g = torch.Generator().manual_seed(M + K + N + 3)
     dz, y = torch.randn(M, N, generator=g).cuda(), torch.randn(M, N, generator=g).cuda()
@@ -440,20 +439,19 @@ def test_pwconv_dgrad_f32_register_kernel(M, K, N, mode):
         ref = ref + res.double()
     outs = {}
     for tag in ('reg', 'reg2', 'tiled'):
-        os.environ.pop('T3D_F32_TILED', None)
-        if tag == 'tiled':
-            os.environ['T3D_F32_TILED'] = '1'
         dx = torch.full((M + 1, K), 7.0, device='cuda')
         nrep = 1 if tag == 'tiled' else 8
         stats = torch.zeros(nrep, 2 * K, device='cuda', dtype=torch.float64)
         Nt.call('t3d_set_reduction_replicas', nrep, 2 * K)
         n0 = Nt.launch_count()
         try:
+            if tag == 'tiled':
+                Nt.call('t3d_pwconv_force_route', Nt.PW_LDS)
             Nt.call('t3d_pwconv_dgrad', Nt.F32, Nt.ptr(dz), Nt.ptr(y), bb, Nt.ptr(wt), Nt.ptr(xraw) if has_x else None, pin,
                     Nt.ptr(res) if with_res else None, Nt.ptr(dx), Nt.ptr(stats) if has_x else None, None, M, 1, K, N, Nt.stream())
         finally:
             Nt.call('t3d_set_reduction_replicas', 1, 0)
-            os.environ.pop('T3D_F32_TILED', None)
+            Nt.call('t3d_pwconv_force_route', Nt.PW_AUTO)
         torch.cuda.synchronize()
         assert Nt.launch_count() - n0 == 1 and torch.all(dx[M] == 7.0)
         outs[tag] = (dx[:M].clone(), stats.sum(0).view(2, K).clone())
@@ -522,13 +520,12 @@ def test_pwconv_wgrad(B, HW, K, N, dt, mode):
 
 
 # fp32 storage, weight gradient of layers with >= 1024 pixels, with the caller's workspace set: the register-operand kernel
-# (csrc/pwconv_f32_wgrad.hip) against fp64 and against round 1's LDS-tiled kernel (T3D_F32_TILED=1); accumulates into dw; ragged
+# (csrc/pwconv_f32_wgrad.hip) against fp64 and against round 1's LDS-tiled kernel (forced route T3D_PW_LDS); accumulates into dw; ragged
 # channel counts on both sides (24, 40, 144: blocks past the matrix edge), ragged pixel counts, bit-identical from run to run
 @pytest.mark.parametrize('M,K,N', [(4096, 16, 96), (3001, 24, 144), (2048, 144, 24), (1031, 96, 576), (1024, 160, 960),
                                    (1100, 960, 160), (100000, 32, 16), (1111, 40, 240), (2000, 8, 8), (5000, 320, 1280)])
 @pytest.mark.parametrize('mode', ['plain', 'relu6', 'hswish'])
 def test_pwconv_wgrad_f32_register_kernel(M, K, N, mode):
-    import os
     from torchdet3d import _native as Nt
     g = torch.Generator().manual_seed(M + K + N + 5)
     dz, y = torch.randn(M, N, generator=g).cuda(), torch.randn(M, N, generator=g).cuda()
@@ -543,17 +540,16 @@ def test_pwconv_wgrad_f32_register_kernel(M, K, N, mode):
     base = torch.randn(N, K, generator=g).cuda()
     outs = {}
     for tag in ('reg', 'reg2', 'tiled'):
-        os.environ.pop('T3D_F32_TILED', None)
-        if tag == 'tiled':
-            os.environ['T3D_F32_TILED'] = '1'
         dw = base.clone()
         Nt.call('t3d_set_workspace', Nt.ptr(ws), ws.numel())
         n0 = Nt.launch_count()
         try:
+            if tag == 'tiled':
+                Nt.call('t3d_pwconv_force_route', Nt.PW_LDS)
             Nt.call('t3d_pwconv_wgrad', Nt.F32, Nt.ptr(dz), Nt.ptr(y), bb, Nt.ptr(x), pro, Nt.ptr(dw), M, 1, K, N, Nt.stream())
         finally:
             Nt.call('t3d_set_workspace', None, 0)
-            os.environ.pop('T3D_F32_TILED', None)
+            Nt.call('t3d_pwconv_force_route', Nt.PW_AUTO)
         torch.cuda.synchronize()
         outs[tag] = (dw - base, Nt.launch_count() - n0)
     assert torch.equal(outs['reg'][0], outs['reg2'][0])
@@ -692,3 +688,70 @@ def test_batch_variance_from_the_one_pass_sums_when_the_mean_dominates(dt, ratio
     rel = ((var - ref).abs() / ref).max().item()
     assert rel < 2e-6 * (1 + (1.5 * ratio) ** 2), rel
     print(f'   {dt} |mean| ~ {ratio} std: worst relative variance error {rel:.1e}')
+
+
+def test_a_refused_pwconv_call_launches_nothing_and_keeps_the_pending_finalize():
+    """The kernel family is picked ahead of every side effect (csrc/pwconv_route.hip): a call no family -- or not the forced one
+    -- can take returns its documented error with no kernel launched, the output untouched and the t3d_fold_request for the
+    coefficients it would read still pending (a later launch can still honour it)."""
+    from torchdet3d import _native as Nt
+    M, HW, N = 64, 16, 32
+    dev = 'cuda'
+    lib = Nt.lib()
+    keep = []
+
+    def fold(kind, C, o):       # a complete t3d_bn_fold in device memory (nobody may read it: the call is refused first)
+        st = torch.zeros(2 * C, device=dev, dtype=torch.float64)
+        mean, invstd, gamma = torch.zeros(C, device=dev), torch.ones(C, device=dev), torch.ones(C, device=dev)
+        spare = [torch.empty(C, device=dev) for _ in range(4 - len(o))]
+        f = Nt.BnFold()
+        f.kind, f.C, f.count, f.nrep, f.rstride, f.eps = kind, C, float(M), 1, 2 * C, 1e-5
+        f.gamma, f.stats, f.mean, f.invstd = Nt.ptr(gamma), Nt.ptr(st), Nt.ptr(mean), Nt.ptr(invstd)
+        f.o0, f.o1, f.o2, f.o3 = (Nt.ptr(t) for t in (*o, *spare))
+        d = torch.frombuffer(bytearray(bytes(f)), dtype=torch.uint8).cuda()
+        keep.extend([st, mean, invstd, gamma, spare, d])
+        return d
+
+    def forward(dtype, code, K, gated=False, stats=False, frag=False):
+        x = torch.randn(M, K, device=dev).to(dtype)
+        w = (torch.zeros(lib.t3d_pwconv_frag_bytes(N, K) // 2, device=dev, dtype=dtype) if frag
+             else torch.randn(N, K, device=dev).to(dtype))
+        sc, sh = torch.rand(K, device=dev) + 0.5, torch.randn(K, device=dev)
+        se = torch.rand(M // HW, K, device=dev) if gated else None
+        pro = Nt.prologue(sc, sh, se, 'relu6', False)
+        out = torch.full((M, N), 7.0, device=dev, dtype=dtype)
+        sums = torch.zeros(2 * N, device=dev, dtype=torch.float64) if stats else None
+        keep.extend([x, w, sh, se, pro, sums])
+        return fold(1, K, (sc, sh)), sc, out, lambda: lib.t3d_pwconv_fwd(code, Nt.ptr(x), pro, Nt.ptr(w), None, Nt.ptr(out), Nt.ptr(sums) if stats else None,
+                                                                          M, HW, K, N, Nt.stream())
+
+    def wgrad_f16(K):
+        dz, y, x = (torch.randn(M, c, device=dev).half() for c in (N, N, K))
+        al, be, ga = (torch.rand(N, device=dev) for _ in range(3))
+        bb = Nt.bnbwd(al, be, ga, False)
+        dw = torch.full((N, K), 7.0, device=dev)
+        keep.extend([dz, y, x, be, ga, bb])
+        return fold(2, N, (al, be, ga)), al, dw, lambda: lib.t3d_pwconv_wgrad(Nt.F16, Nt.ptr(dz), Nt.ptr(y), bb, Nt.ptr(x), None, Nt.ptr(dw), M, HW, K, N,
+                                                                             Nt.stream())
+
+    bf, fp = torch.bfloat16, torch.float16
+    cases = [(forward(fp, Nt.F16, 32, stats=True), Nt.PW_AUTO, Nt.ERR_UNSUPPORTED),                            # fp16 is inference: no BatchNorm sums
+             (forward(bf, Nt.BF16 | Nt.W_FRAG, 1928, gated=True, frag=True), Nt.PW_AUTO, Nt.ERR_UNSUPPORTED),   # too deep to stream, gated
+             (forward(bf, Nt.BF16, 64), Nt.PW_DEEP, Nt.ERR_UNSUPPORTED),
+             (wgrad_f16(32), Nt.PW_AUTO, Nt.ERR_ARG)]
+    outs = []
+    try:
+        for (desc, key, out, call), forced, want in cases:
+            Nt.call('t3d_pwconv_force_route', forced)
+            Nt.call('t3d_fold_request', Nt.ptr(desc), Nt.ptr(key))
+            before = Nt.launch_count()
+            rc = call()
+            assert rc == want, (rc, want)
+            assert Nt.launch_count() == before
+            assert lib.t3d_fold_pending() == 1 and lib.t3d_fold_pending() == 0
+            outs.append(out)
+    finally:
+        lib.t3d_fold_pending()
+        Nt.call('t3d_pwconv_force_route', Nt.PW_AUTO)
+    torch.cuda.synchronize()
+    assert len(outs) == 4 and all((o == 7.0).all() for o in outs)

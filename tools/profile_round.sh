@@ -10,7 +10,6 @@ python3 bench.py --full --steps 30 --warmup 8 --eval --no-cpu-baseline > $o/benc
 python3 bench.py --full --steps 30 --warmup 8 --eval --eval-dtype bf16 --no-cpu-baseline > $o/bench_eval_bf16_optin.json 2> /dev/null
 python3 bench.py --full --steps 30 --warmup 8 --eval --eval-sync --no-cpu-baseline > $o/bench_eval_val_step.json 2> /dev/null
 python3 bench.py --full --steps 30 --warmup 8 --eval --eval-sync --eval-dtype bf16 --no-cpu-baseline > $o/bench_eval_bf16_optin_val_step.json 2> /dev/null
-T3D_F32_TILED=1 python3 bench.py --full --steps 30 --warmup 8 --eval --no-cpu-baseline > $o/bench_eval_f32_tiled_kernel.json 2> /dev/null
 python3 bench.py --full --steps 20 --warmup 5 --model mobilenetv3_large --no-cpu-baseline > $o/bench_mnv3_large.json 2> /dev/null
 python3 bench.py --full --steps 20 --warmup 5 --model mobilenetv3_small --no-cpu-baseline > $o/bench_mnv3_small.json 2> /dev/null
 python3 bench.py --full --steps 30 --warmup 8 --eval --eval-dtype f16 --no-cpu-baseline > $o/bench_eval_f16.json 2> /dev/null

@@ -1,5 +1,5 @@
 """Isolated timing of the fp32-storage inference 1x1 conv on MobileNetV2's layer shapes at batch 256: the register-operand kernel
-(csrc/pwconv_f32_reg.hip) against round 1's LDS-tiled one (T3D_F32_TILED=1).
+(csrc/pwconv_f32_reg.hip) against round 1's LDS-tiled one (t3d_pwconv_force_route(T3D_PW_LDS)).
 usage: python tools/time_pw_f32.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,11 +32,10 @@ for hw, K, Nn, cnt in [(112, 32, 16, 1), (112, 16, 96, 1), (56, 96, 24, 1), (56,
     pro = N.prologue(sc, sh, None, 'relu6', False)
     y = torch.empty(M, Nn, device='cuda')
     f = lambda: N.call('t3d_pwconv_fwd', N.F32, N.ptr(x), pro, N.ptr(w), None, N.ptr(y), None, M, hw * hw, K, Nn, N.stream())
-    os.environ.pop('T3D_F32_TILED', None)
     t0 = timeit(f)
-    os.environ['T3D_F32_TILED'] = '1'
+    N.call('t3d_pwconv_force_route', N.PW_LDS)
     t1 = timeit(f)
-    os.environ.pop('T3D_F32_TILED', None)
+    N.call('t3d_pwconv_force_route', N.PW_AUTO)
     gb = M * (K + Nn) * 4 / 1e3
     tot[0] += cnt * t0; tot[1] += cnt * t1
     print(f'{hw:4d}^2 {K:4d}->{Nn:4d} x{cnt}: reg {t0:6.1f} us {gb / t0:5.0f} GB/s {2e-6 * M * K * Nn / t0:5.1f} TF/s  tiled {t1:6.1f} us')

@@ -1,6 +1,6 @@
 """Isolated timing of the fp32-storage TRAINING 1x1 kernels on MobileNetV2's layer shapes at batch 256: forward with BatchNorm sums,
 data gradient, weight gradient -- the register-operand kernels (csrc/pwconv_f32_reg.hip, csrc/pwconv_f32_wgrad.hip) against round
-1's LDS-tiled ones (T3D_F32_TILED=1).   usage: python tools/time_pw_f32_bwd.py"""
+1's LDS-tiled ones (t3d_pwconv_force_route(T3D_PW_LDS)).   usage: python tools/time_pw_f32_bwd.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, '3d-object-detection.pytorch_amd')]
@@ -20,11 +20,10 @@ def timeit(fn, n=10):
     return e0.elapsed_time(e1) / n * 1e3
 
 def both(fn):
-    os.environ.pop('T3D_F32_TILED', None)
     t0 = timeit(fn)
-    os.environ['T3D_F32_TILED'] = '1'
+    N.call('t3d_pwconv_force_route', N.PW_LDS)
     t1 = timeit(fn)
-    os.environ.pop('T3D_F32_TILED', None)
+    N.call('t3d_pwconv_force_route', N.PW_AUTO)
     return t0, t1
 
 B = 256
