@@ -2,7 +2,8 @@
 
 A DataLoader (workers, pinned memory) yields the host side of a batch -- crops packed in one buffer plus a descriptor
 table (`collate_crops`).  For each batch the main process draws the augmentation parameters, builds the kernel records and
-the keypoints, uploads, and launches `t3d_augment_crops_u8` once.  With `prefetch` >= 1 that work runs on a copy stream
+the keypoints, uploads, and launches `t3d_augment_crops_u8` once (a pipeline with random_rescale, hue_saturation_value or
+color_jitter: `t3d_augment_chain_crops_u8`, with a second record per sample in the same upload).  With `prefetch` >= 1 that work runs on a copy stream
 `prefetch` batches ahead of the consumer, and each batch is handed over with an event the consumer's stream waits on, so
 batch i + 1 is uploaded and augmented while step i runs.  `prefetch = 0` does it synchronously on the consumer's stream.
 
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .objectron import AUG_SAMPLE_DTYPE, collate_crops
+from .objectron import AUG_SAMPLE_DTYPE, chain_scratch_bytes, chain_stages, collate_crops
 
 __all__ = ['GpuAugmentLoader']
 
@@ -118,16 +119,22 @@ class GpuAugmentLoader:
         epoch = int(getattr(self.loader.sampler, 'epoch', 0))
         prm = self.pipeline.draw(B, (self.seed, epoch, self.rank) + tuple(key_tail))
         rec = self.pipeline.records(where, prm)
+        ext = None
+        if self.pipeline.chained:
+            rec, ext = rec
         kp = self.pipeline.keypoints(kp64, dnp, prm)
-        # one pinned upload for records | keypoints | classes (each part 8-byte aligned)
+        # one pinned upload for records | keypoints | classes [| chain records] (each part 8-byte aligned)
         nrec, nkp = B * rec.dtype.itemsize, B * 18 * 4
         nkp8 = (nkp + 7) // 8 * 8
-        total = nrec + nkp8 + B * 8
+        next_ = nrec + nkp8 + B * 8
+        total = next_ + (B * ext.dtype.itemsize if ext is not None else 0)
         slot = self._staging(total)
         host = slot[0]
         host[:nrec].numpy()[...] = rec.view(np.uint8)
         host[nrec:nrec + nkp].numpy()[...] = kp.reshape(-1).view(np.uint8)
-        host[nrec + nkp8:total].numpy()[...] = cats.astype(np.int64).view(np.uint8)
+        host[nrec + nkp8:next_].numpy()[...] = cats.astype(np.int64).view(np.uint8)
+        if ext is not None:
+            host[next_:total].numpy()[...] = ext.view(np.uint8)
         dev = torch.device('cuda', torch.cuda.current_device())
         stream = torch.cuda.current_stream(dev)
         if prefetch > 0:
@@ -140,14 +147,18 @@ class GpuAugmentLoader:
             slot[1] = torch.cuda.Event()
             slot[1].record(stream)
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
-            if packed is None:
-                N.call('t3d_augment_resized_u8', N.ptr(self._arena), self._arena.numel(), N.ptr(meta), N.ptr(imgs), B, oh, ow,
-                       N.stream())
-            else:
-                src = packed.to(dev, non_blocking=True)
-                N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
+            src = self._arena if packed is None else packed.to(dev, non_blocking=True)
+            if ext is None:
+                N.call('t3d_augment_resized_u8' if packed is None else 't3d_augment_crops_u8', N.ptr(src), src.numel(),
+                       N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
+            elif B:
+                stages = chain_stages(rec, ext)
+                scratch = torch.empty(max(chain_scratch_bytes(B, oh, ow, stages), 8), dtype=torch.uint8, device=dev)
+                N.call('t3d_augment_chain_resized_u8' if packed is None else 't3d_augment_chain_crops_u8', N.ptr(src),
+                       src.numel(), N.ptr(meta), N.ptr(meta[next_:total]), N.ptr(scratch), scratch.numel(), N.ptr(imgs), B,
+                       oh, ow, stages, N.stream())
             kp_d = meta[nrec:nrec + nkp].view(torch.float32).view(B, 9, 2)
-            cats_d = meta[nrec + nkp8:total].view(torch.int64)
+            cats_d = meta[nrec + nkp8:next_].view(torch.int64)
         if prefetch > 0:
             ready = torch.cuda.Event()
             ready.record(stream)

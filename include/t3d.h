@@ -305,6 +305,54 @@ int t3d_augment_crops_u8(const unsigned char* src, long long src_bytes, const vo
 int t3d_augment_resized_u8(const unsigned char* arena, long long arena_bytes, const void* samples, unsigned char* out, int B,
                            int oh, int ow, void* stream);
 
+/* The augmentations of a pipeline that also names random_rescale (utils/transforms.py:20-47), hue_saturation_value or
+ * color_jitter (builders/loader_builder.py:38-52), at most four launches (csrc/augment_chain.hip).  Per sample, with uint8
+ * rounding after each step that yields an image:
+ *   resize to (oh, ow), T3D_AUG_FLIP, T3D_AUG_LUT   as t3d_augment_crops_u8 (the base record `samples[i]`),
+ *   the colour program `chains[i]`                  ops[0 .. n_ops) in order, each on the whole uint8 image:
+ *     T3D_CHAIN_LUT         lut[i] = (uint8) clip(float32(i) * float32(p0) + float32(p1), 0, 255)   (T3D_AUG_LUT's arithmetic),
+ *     T3D_CHAIN_HSV         RGB -> HSV (8-bit, H in 0..179), H = (uint8) mod(H + p0, 180), S = (uint8) clip(S + p1, 0, 255),
+ *                           V = (uint8) clip(V + p2, 0, 255) in fp64 (numpy's mod: the sign of the divisor), HSV -> RGB,
+ *     T3D_CHAIN_BRIGHTNESS  lut[i] = (uint8) clip(i * p0, 0, 255) in fp64,
+ *     T3D_CHAIN_CONTRAST    lut[i] = (uint8) clip(i * p0 + mean * (1 - p0), 0, 255) in fp64; mean = (integer sum of the grey
+ *                           image the op meets) / (oh * ow) in fp64.  At most one per program,
+ *     T3D_CHAIN_SATURATION  rint(float32(x) * float32(p0) + float32(grey) * float32(1 - p0)), half to even, saturated,
+ *     T3D_CHAIN_HUE         T3D_CHAIN_HSV with shifts (180 * p0, 0, 0),
+ *     grey = (9798 R + 19235 G + 3735 B + 2^14) >> 15; the 8-bit HSV pair is restated at the top of csrc/augment_chain.hip,
+ *   T3D_AUG_ROTATE        the first warp: cv::warpAffine INTER_LINEAR, border 0, through the inverse map m of the base record,
+ *   T3D_CHAIN_WARP2       the second warp, through chains[i].m2, of the first warp's uint8 result (needs T3D_AUG_ROTATE),
+ *   T3D_AUG_SWAP_RB       RGB -> BGR.
+ * `stages` names the passes some record needs: T3D_STAGE_MEAN (a T3D_CHAIN_CONTRAST op: a reduction launch in front of the
+ * colour launch), T3D_STAGE_WARP (T3D_AUG_ROTATE), T3D_STAGE_WARP2 (T3D_CHAIN_WARP2); a pass that is not named is not
+ * launched.  A bad record gives a zero image and leaves the other samples alone: a base record t3d_augment_crops_u8
+ * refuses, n_ops outside 0..8, an unknown op kind or flag, a second CONTRAST op, T3D_CHAIN_WARP2 without T3D_AUG_ROTATE,
+ * or a record that needs a stage `stages` does not name.
+ * samples: [B] t3d_aug_sample, chains: [B] t3d_aug_chain, both in DEVICE memory.  scratch: device memory, 8-byte aligned,
+ * scratch_bytes >= 8 * B (the grey sums; zeroed by the call) + r * B * oh * ow * 3 rounded up to a multiple of 8, r = the
+ * number of warp stages named (the uint8 images between the passes).  out [B, oh, ow, 3] uint8, 4-byte aligned.  B <= 65535.
+ * With n_ops == 0 and no second warp the output equals t3d_augment_crops_u8 of the same base records, bit for bit. */
+enum { T3D_CHAIN_LUT = 1, T3D_CHAIN_HSV = 2, T3D_CHAIN_BRIGHTNESS = 3, T3D_CHAIN_CONTRAST = 4, T3D_CHAIN_SATURATION = 5,
+       T3D_CHAIN_HUE = 6 };
+enum { T3D_CHAIN_WARP2 = 1 };
+enum { T3D_STAGE_MEAN = 1, T3D_STAGE_WARP = 2, T3D_STAGE_WARP2 = 4 };
+#define T3D_CHAIN_MAX_OPS 8
+typedef struct {
+  int n_ops;                         /* 0 .. T3D_CHAIN_MAX_OPS */
+  int flags;                         /* T3D_CHAIN_WARP2 */
+  int kind[T3D_CHAIN_MAX_OPS];       /* T3D_CHAIN_* of each op */
+  double p[T3D_CHAIN_MAX_OPS][3];    /* its parameters (fp64) */
+  double m2[6];                      /* T3D_CHAIN_WARP2: output pixel -> coordinate in the first warp's result, row-major 2x3 */
+} t3d_aug_chain;                     /* 280 bytes */
+int t3d_augment_chain_crops_u8(const unsigned char* src, long long src_bytes, const void* samples, const void* chains,
+                               void* scratch, long long scratch_bytes, unsigned char* out, int B, int oh, int ow, int stages,
+                               void* stream);
+
+/* t3d_augment_chain_crops_u8 over an arena of crops that were resized once (the records t3d_augment_resized_u8 takes):
+ * the same template over another source, so the two agree bit for bit as t3d_augment_resized_u8 / t3d_augment_crops_u8 do. */
+int t3d_augment_chain_resized_u8(const unsigned char* arena, long long arena_bytes, const void* samples, const void* chains,
+                                 void* scratch, long long scratch_bytes, unsigned char* out, int B, int oh, int ow, int stages,
+                                 void* stream);
+
 /* Materialise a block output:  z = act(scale*y + shift) + residual   (residual may be NULL; scale NULL = identity).
  * Replaces the BatchNorm normalise pass + `x + self.conv(x)` (mobilenetv3.py:159,162-164). y,z,residual [M,C]. */
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,

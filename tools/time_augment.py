@@ -2,11 +2,14 @@
 
   1. HIP-event time of one `t3d_augment_crops_u8` launch at B = 164 and 256, 224x224 output, crop sizes drawn like Objectron
      boxes (150 - 500 px a side), all augmentations at the default config's rates; also with every sample rotated.
+     With --chain also `t3d_augment_chain_crops_u8` (csrc/augment_chain.hip) on the same crops: the default pipeline plus
+     hue_saturation_value, color_jitter and random_rescale, every transform at p = 1 (four launches a batch).
   2. Loader batches/s with num_workers 0 / 8 / 16 over a generated directory of 960x720 JPEGs (Pillow decode + crop in the
      workers, draws + upload + kernel in the main process), nothing else running.  256 JPEG files, `--objects` annotations
      cycling over them (every object decodes its frame, as Objectron does); the timing starts after the first batch.
   3. `Trainer.train(epoch)` crops/s (MobileNetV3-large, bf16, the default step plan) over the same loader.
-Prints one JSON line per measurement.  Usage: python tools/time_augment.py [--objects N] [--batch B] [--workers 0,8,16]"""
+Prints one JSON line per measurement.
+Usage: python tools/time_augment.py [--objects N] [--batch B] [--workers 0,8,16] [--chain] [--kernels-only]"""
 import argparse
 import json
 import os
@@ -23,13 +26,16 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def kernel_time(B, rotate_all=False, reps=50):
+def kernel_time(B, rotate_all=False, reps=50, chain=False):
     from torchdet3d import _native as N
-    from torchdet3d.dataloaders.objectron import AugmentPipeline
+    from torchdet3d.dataloaders.objectron import AugmentPipeline, chain_scratch_bytes, chain_stages
     import augment_ref as R
     tr, _ = R.default_pipelines((224, 224))
-    if rotate_all:
-        tr = [(n, dict(a, p=1.0) if n in ('random_rotate', 'horizontal_flip', 'random_brightness_contrast') else a) for n, a in tr]
+    if chain:
+        tr = tr[:4] + [('hue_saturation_value', dict()), ('color_jitter', dict()), ('random_rescale', dict(scale_limit=(0.8, 1.25))),
+                       tr[4]] + tr[5:]
+    if rotate_all or chain:
+        tr = [(n, a if n in ('convert_color', 'resize', 'normalize', 'to_tensor') else dict(a, p=1.0)) for n, a in tr]
     pipe = AugmentPipeline(tr, R.NORMALIZATION)
     rng = np.random.default_rng(B)
     hw = rng.integers(150, 501, (B, 2))
@@ -37,20 +43,31 @@ def kernel_time(B, rotate_all=False, reps=50):
     desc = np.stack([np.concatenate([[0], np.cumsum(sizes)[:-1]]), hw[:, 0], hw[:, 1]], 1).astype(np.int64)
     src = torch.randint(0, 256, (int(sizes.sum()),), dtype=torch.uint8, device='cuda')
     rec = pipe.records(desc, pipe.draw(B, (0, 0, 0, 0)))
-    recd = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
     out = torch.empty(B, 224, 224, 3, dtype=torch.uint8, device='cuda')
-    args = (N.ptr(src), src.numel(), N.ptr(recd), N.ptr(out), B, 224, 224)
+    if chain:
+        rec, ext = rec
+        stages = chain_stages(rec, ext)
+        extd = torch.from_numpy(ext.view(np.uint8).copy()).cuda()
+        scratch = torch.empty(chain_scratch_bytes(B, 224, 224, stages), dtype=torch.uint8, device='cuda')
+    recd = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
+    if chain:
+        name = 't3d_augment_chain_crops_u8'
+        args = (N.ptr(src), src.numel(), N.ptr(recd), N.ptr(extd), N.ptr(scratch), scratch.numel(), N.ptr(out), B, 224, 224, stages)
+    else:
+        name = 't3d_augment_crops_u8'
+        args = (N.ptr(src), src.numel(), N.ptr(recd), N.ptr(out), B, 224, 224)
     for _ in range(5):
-        N.call('t3d_augment_crops_u8', *args, N.stream())
+        N.call(name, *args, N.stream())
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
     for e0, e1 in ev:
         e0.record()
-        N.call('t3d_augment_crops_u8', *args, N.stream())
+        N.call(name, *args, N.stream())
         e1.record()
     torch.cuda.synchronize()
     t = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)
-    return dict(what='kernel', B=B, rotate_all=rotate_all, median_us=round(t[len(t) // 2], 2), min_us=round(t[0], 2),
-                crop_MB=round(src.numel() / 1e6, 1), out_MB=round(out.numel() / 1e6, 1))
+    return dict(what='kernel', entry=name, B=B, rotate_all=rotate_all or chain, median_us=round(t[len(t) // 2], 2),
+                min_us=round(t[0], 2), max_us=round(t[-1], 2), crop_MB=round(src.numel() / 1e6, 1),
+                out_MB=round(out.numel() / 1e6, 1))
 
 
 def make_frames(root, n, files=256):
@@ -131,10 +148,16 @@ def main():
     ap.add_argument('--batch', type=int, default=164)
     ap.add_argument('--workers', default='0,8,16')
     ap.add_argument('--train-workers', type=int, default=16)
+    ap.add_argument('--chain', action='store_true', help='also time t3d_augment_chain_crops_u8, every transform at p = 1')
+    ap.add_argument('--kernels-only', action='store_true', help='stop after the kernel timings (no frames, loader or training)')
     a = ap.parse_args()
     for B in (164, 256):
         for rot in (False, True):
             print(json.dumps(kernel_time(B, rot)), flush=True)
+        if a.chain:
+            print(json.dumps(kernel_time(B, chain=True)), flush=True)
+    if a.kernels_only:
+        return
     with tempfile.TemporaryDirectory() as root:
         t0 = time.perf_counter()
         make_frames(root, a.objects)
