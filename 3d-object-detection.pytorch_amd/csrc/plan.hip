@@ -81,11 +81,11 @@ const Entry kEntries[] = {
     T3D_E(t3d_zero_batched), T3D_E(t3d_copy_cols), T3D_E(t3d_bn_bias_grad), T3D_E(t3d_se_bwd_affine), T3D_E(t3d_dropout_mask),
     T3D_E(t3d_loss_fwd_bwd), T3D_E(t3d_metrics_per_sample), T3D_E(t3d_iou3d), T3D_E(t3d_box_iou3d), T3D_E(t3d_ssd_decode_nms),
     T3D_E(t3d_expdw_fwd), T3D_E(t3d_track_step), T3D_E(t3d_ssd_select_rects), T3D_E(t3d_head_select), T3D_E(t3d_track_kp_to_frame),
-    T3D_E(t3d_objectron_pairs), T3D_E(t3d_objectron_hitmiss), T3D_E(t3d_draw_overlays_u8),
+    T3D_E(t3d_objectron_pairs), T3D_E(t3d_objectron_hitmiss), T3D_E(t3d_draw_overlays_u8), T3D_E(t3d_ssd_multibox_loss),
 };
 #undef T3D_E
 constexpr int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));
-constexpr int kMaxArgs = 24;
+constexpr int kMaxArgs = 32;       // (t3d_ssd_multibox_loss takes 29)
 
 enum OpKind { OP_CALL = 0, OP_FORK = 1, OP_COPY_D2H = 2, OP_EVENT_RECORD = 3 };
 enum ArgKind { ARG_WORD = 0, ARG_STRUCT = 1, ARG_SLOT = 2 };

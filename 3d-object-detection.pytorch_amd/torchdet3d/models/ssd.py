@@ -13,6 +13,9 @@ unpinned** (no source, no weights); the layers themselves are the product's own 
              with bias (t3d_pwconv_fwd); class branch A*(classes+1) channels (background last), box branch A*4
   post       t3d_ssd_decode_nms: decode + softmax + per-class NMS in one launch; the overall top-`max_per_img` on the host
              (`detect`) or on the device (`detect_device` + t3d_ssd_select_rects: utils/pipeline.py)
+  loss       `loss`: the config's training half :41-55 (targets, MultiBox loss, gradients with respect to the head outputs)
+             through t3d_ssd_multibox_loss (losses/detection_losses.py).  The backward through the heads and the tapped
+             backbone and a detection loader are NOT built: the detector cannot be trained end to end yet.
 """
 import ctypes
 import math
@@ -69,6 +72,11 @@ def head_param_shapes(num_classes=len(CLASSES)):
 class SSD300:
     """`detect(frames_u8)` -> per image an [n, 6] array (x1, y1, x2, y2 normalised to [0, 1], score, label)."""
 
+    # config :41-55: the assigner's thresholds and the head's loss settings (the entries this project builds; the same lines'
+    # `loss_balancing=True` is the fork's own learnable weighting, has no published definition and is not built)
+    TRAIN_CFG = dict(pos_iou_thr=0.4, neg_iou_thr=0.4, min_pos_iou=0., gt_max_assign_all=False, smoothl1_beta=1.,
+                     neg_pos_ratio=3)
+
     def __init__(self, device='cuda', dtype=torch.bfloat16, num_classes=len(CLASSES), score_thr=0.02, iou_thr=0.45,
                  max_per_img=200, seed=0):
         self.device, self.dtype, self.nc = torch.device(device), dtype, num_classes
@@ -91,6 +99,7 @@ class SSD300:
         self._packed = None
         self._stds = (ctypes.c_float * 4)(*STDS)
         self._persist, self._hbufs, self._dev = False, {}, {}
+        self._mbox = None
 
     def state_dict(self):
         sd = {'backbone.' + k: v for k, v in self.backbone.state_dict().items()
@@ -161,6 +170,21 @@ class SSD300:
                 res.append(o)
             outs.append((res[0], res[1], H * W))
         return outs
+
+    @torch.no_grad()
+    def loss(self, imgs, gt_boxes, gt_labels, gt_counts, with_grads=False):
+        """`head_outputs` (BatchNorm in eval mode, as everywhere in this class) followed by the MultiBox loss of TRAIN_CFG:
+        gt_boxes [B,G,4] fp32 in input pixels, gt_labels [B,G] int32, gt_counts [B] int32 -> `MultiBoxLoss.from_heads`'
+        dict (the validation loss of the loaded checkpoint; with `with_grads` the gradients with respect to the head
+        outputs, which a backward through the heads would consume).  Nothing is synchronised."""
+        if self._mbox is None:
+            from ..losses.detection_losses import MultiBoxLoss
+            t = self.TRAIN_CFG
+            self._mbox = MultiBoxLoss(self.anchors, self.nc, t['pos_iou_thr'], t['neg_iou_thr'], t['min_pos_iou'],
+                                      t['neg_pos_ratio'], t['smoothl1_beta'], STDS)
+        outs = self.head_outputs(imgs)
+        return self._mbox.from_heads(outs, gt_boxes, gt_labels, gt_counts, with_grads=with_grads,
+                                     nanchors=[len(WIDTHS[l]) for l in range(len(outs))])
 
     @torch.no_grad()
     def detect_device(self, imgs):

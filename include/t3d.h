@@ -531,6 +531,41 @@ int t3d_ssd_decode_nms(int dtype, int nlevels, const void* const* cls, const voi
                        int num_classes, float score_thr, float iou_thr, int max_per_class, float img_w, float img_h,
                        const float* stds, float* out, int* counts, void* stream);
 
+/* MultiBox training loss of the SSD detector and its gradients with respect to the head outputs (csrc/ssd_loss.hip; the
+ * training half of configs/detection/mnv2_ssd_300_2_heads.py:41-55: MaxIoUAssigner(pos_iou_thr = neg_iou_thr = 0.4,
+ * min_pos_iou = 0, gt_max_assign_all = False), smoothl1_beta = 1, neg_pos_ratio = 3), two launches, nothing read back.
+ * Arithmetic per the published mmdet 2.x SSDHead.loss / MaxIoUAssigner / DeltaXYWHBBoxCoder / smooth_l1_loss, restated in
+ * tests/ssd_loss_ref.py; parity with the reference's detector is unpinned (the fork is external); the config's
+ * loss_balancing has no published definition and is not built.
+ *   dtype .. reg_stride, anchors: as t3d_ssd_decode_nms (pad channels are never read); A = sum hw*nanchors;
+ *   gt_boxes [B][G][4] fp32 (x1, y1, x2, y2 in input pixels), gt_labels [B][G] int32, gt_counts [B] int32 clamped to
+ *   [0, G]; a slot below the count is used when its coordinates are finite, x2 > x1, y2 > y1 and 0 <= label < num_classes,
+ *   and skipped as if absent otherwise.
+ * Per image: IoU in fp32, every operation rounded on its own; assigned[a] = the first ground truth of the largest IoU when
+ * that is >= pos_iou_thr, else -1; then, ground truths ascending, the LOWEST anchor of the largest IoU is given to the ground
+ * truth when that IoU >= min_pos_iou (a later one overrides; with min_pos_iou = 0 a ground truth that overlaps nothing takes
+ * anchor 0); positives carry gt_labels[assigned], all others the background class num_classes; ce in fp32 (expf / logf);
+ * the k = min(neg_pos_ratio * num_pos, num_neg) negatives first by (ce descending on the fp32 bit pattern, anchor ascending)
+ * are mined; box targets ((gx-px)/pw, (gy-py)/ph, log(gw/pw), log(gh/ph)) / stds, smooth L1 with beta.
+ * Over the batch, avg = max(sum num_pos, 1):
+ *   scalars [4] fp64 = loss_cls (ce of positives and mined negatives / avg), loss_bbox (/ avg), total_pos, total_mined;
+ *   sums in fp64 over a fixed tree (no floating-point atomics: two runs are bit-identical);
+ *   num_pos [B] int32; assigned [B][A] int32: ground-truth index, -1 unused negative, -2 mined negative;
+ *   dcls / dreg: HOST arrays of nlevels fp32 device pointers in the rows and strides of cls / reg:
+ *   dcls = (softmax - onehot(label)) / avg on positives and mined negatives, dreg = smoothl1'(reg - t) / avg on positives,
+ *   0 elsewhere, pad channels included; both NULL = losses only.
+ *   work: t3d_ssd_multibox_work_bytes(B, A) bytes of device scratch, 8-byte aligned (RETURNS the byte count, or T3D_ERR_ARG).
+ * T3D_ERR_ARG: NULL or misaligned arguments, G < 0, nlevels outside 1..2, only one of dcls / dreg, beta <= 0,
+ * neg_pos_ratio < 0, work_bytes too small.  T3D_ERR_UNSUPPORTED: neg_iou_thr != pos_iou_thr (no ignore band), A > 16384 or
+ * G > 64 (the per-anchor state of an image lives in LDS), B * A >= 2^31.  B == 0 returns T3D_OK without a launch. */
+int t3d_ssd_multibox_work_bytes(int B, int A);
+int t3d_ssd_multibox_loss(int dtype, int nlevels, const void* const* cls, const void* const* reg, const int* hw,
+                          const int* nanchors, const int* cls_stride, const int* reg_stride, const float* anchors,
+                          const float* gt_boxes, const int* gt_labels, const int* gt_counts, int B, int G, int num_classes,
+                          float pos_iou_thr, float neg_iou_thr, float min_pos_iou, int neg_pos_ratio, float beta,
+                          const float* stds, void* work, long long work_bytes, double* scalars, int* num_pos, int* assigned,
+                          void* const* dcls, void* const* dreg, void* stream);
+
 /* The demo's third stage: IOUTracker.process + get_tracked_objects of torchdet3d/utils/tracking_tools.py:127-290 (Track:
  * :9-124; call site scripts/demo.py:56-78), one frame of S independent streams (cameras) per launch, one workgroup per
  * stream; the whole tracker state lives in device memory and nothing is read back.  Per stream, in the reference's order:
