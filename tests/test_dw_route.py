@@ -132,3 +132,88 @@ def test_a_forced_route_is_taken_wherever_its_kernels_can_and_refused_elsewhere(
     finally:
         assert force(N.DW_AUTO) == 0
     _check_rows()
+
+
+# ---- the parity case table (tests/dw_cases.py): every row reaches the family it names, no cell of a family is left without rows
+
+FAMILY = dict(TILE=TILE, ROW3=ROW3, PLANE7=PLANE7, ROWK=ROWK, LDS=LDS)
+DTYPE = dict(f32=F32, bf16=BF16, f16=F16)
+
+
+def _row_route(c):
+    return route(c.direction == 'bwd', c.k, c.stride, c.H, c.W, c.C, dtype=DTYPE[c.dtype], B=c.B, gated=c.gated, pooled=c.pooled)
+
+
+def _cells():
+    """Every (direction, family, k, stride, dtype) for which the family's `can` accepts some call of the sweep's grid: the
+    forced route asks `can` alone."""
+    force = N.lib().t3d_dwconv_force_route
+    sides = (1, 2, 3, 7, 8, 14, 15, 28, 29, 56, 64, 65)
+    cells = set()
+    try:
+        for name, fam in FAMILY.items():
+            assert force(fam) == 0
+            for backward, k, s, dtype in itertools.product((0, 1), (3, 5), (1, 2), DTYPE):
+                if any(route(backward, k, s, H, W, C, dtype=DTYPE[dtype], B=B, gated=g, pooled=p) == fam
+                       for H, W, C, p, g, B in itertools.product(sides, sides, (8, 24, 72, 960), (0, 1), (0, 1), (1, 256))):
+                    cells.add((('fwd', 'bwd')[backward], name, k, s, dtype))
+    finally:
+        assert force(N.DW_AUTO) == 0
+    return cells
+
+
+def test_every_parity_case_reaches_the_family_it_names():
+    from dw_cases import CASES
+    force = N.lib().t3d_dwconv_force_route
+    assert len(set(CASES)) == len(CASES)
+    for c in CASES:
+        assert c.direction in ('fwd', 'bwd') and c.family in FAMILY and c.dtype in DTYPE
+        # what the GPU test passes follows from the row: gap_sum from `pooled`, the gate from the mode, no pooled sums without statistics
+        assert c.gated == int(c.mode.startswith('se')) and (c.stats or not c.pooled) and (c.direction == 'fwd' or not c.pooled)
+        auto = _row_route(c)
+        if not c.forced:
+            assert auto == FAMILY[c.family], c
+        else:
+            assert auto >= 0 and auto != FAMILY[c.family], c       # (a forced row the dispatcher sends there anyway is mislabelled)
+            try:
+                assert force(FAMILY[c.family]) == 0
+                assert _row_route(c) == FAMILY[c.family], c
+            finally:
+                assert force(N.DW_AUTO) == 0
+
+
+def test_every_cell_of_every_family_has_parity_cases():
+    from dw_cases import BWD_ACT_MODES, BWD_MODES, CASES
+    cells = _cells()
+    assert (sum(c[0] == 'fwd' for c in cells), sum(c[0] == 'bwd' for c in cells)) == (36, 26)
+    rows = {}
+    for c in CASES:
+        rows.setdefault((c.direction, c.family, c.k, c.stride, c.dtype), []).append(c)
+    assert set(rows) <= cells                                        # (a row outside every `can` would have failed the test above)
+    for cell in sorted(cells):
+        assert len(rows.get(cell, ())) >= 2, cell
+    fwd_fd = {(c[1], c[4]) for c in cells if c[0] == 'fwd'}
+    for fam, dt in sorted(fwd_fd):
+        mine = [c for c in CASES if c.direction == 'fwd' and (c.family, c.dtype) == (fam, dt)]
+        modes = {c.mode for c in mine}
+        assert {'plain', 'bnact-none', 'bnact-relu', 'bnact-relu6', 'bnact-hswish'} <= modes, (fam, dt)
+        assert ({'se_pre', 'se_post'} <= modes) == (fam == 'LDS'), (fam, dt)
+        assert any(not c.stats and not c.pooled for c in mine), (fam, dt)
+        # pooled sums: every family but the 3x3 row walk takes them
+        assert {c.pooled for c in mine} == ({0} if fam == 'ROW3' else {0, 1}), (fam, dt)
+    # the packed clamp form of ReLU6: bf16 at stride 2 in the 3x3 row walk (stride 1: the column-pair kernel's own)
+    for s in (1, 2):
+        assert any(c.mode == 'bnact-relu6' for c in rows[('fwd', 'ROW3', 3, s, 'bf16')])
+    for fam in {c[1] for c in cells if c[0] == 'bwd'}:
+        for dt in ('f32', 'bf16'):
+            modes = {c.mode for c in CASES if c.direction == 'bwd' and (c.family, c.dtype) == (fam, dt)}
+            # (the LDS tiles take the activation as a run-time argument of the functions every family shares)
+            assert modes == set(BWD_MODES if fam == 'LDS' else BWD_ACT_MODES), (fam, dt)
+    # the 3x3 row walk instantiates its backward kernels per activation (bf16 ReLU6: the packed clamp form, at either stride)
+    for cell in cells:
+        if cell[:2] == ('bwd', 'ROW3'):
+            assert {'bnact', 'bnact-relu6', 'bnact-relu', 'plain_res'} <= {c.mode for c in rows[cell]}, cell
+    # the LDS-tiled backward: every mode in every cell
+    for cell in cells:
+        if cell[:2] == ('bwd', 'LDS'):
+            assert {c.mode for c in rows[cell]} == set(BWD_MODES), cell

@@ -1,4 +1,6 @@
 """GPU parity: depthwise conv forward + BN statistics through the C ABI vs the torch-CPU oracle ops."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -27,19 +29,56 @@ SHAPES = [  # B, C, H, W, k, s
     (2, 120, 28, 28, 5, 1), (3, 40, 14, 14, 5, 1), (2, 48, 9, 13, 5, 1), (2, 72, 56, 56, 5, 2), (3, 24, 10, 15, 5, 2)]
 
 
-@pytest.mark.parametrize('B,C,H,W,k,s', SHAPES)
-@pytest.mark.parametrize('dt', ['f32', 'bf16'])
-@pytest.mark.parametrize('mode', ['plain', 'bnact', 'se_pre', 'se_post'])
-def test_dwconv_fwd(B, C, H, W, k, s, dt, mode):
+DTYPES = {'f32': torch.float32, 'bf16': torch.bfloat16, 'f16': torch.float16}
+# output tolerance per storage type: fp32 accumulation order; bf16: 2^-8 unit roundoff of the stored value and the staged
+# operand; fp16: the bf16 figure scaled by the ratio of unit roundoffs, 2e-2 * 2^-11 / 2^-8 (the fp32-accumulated reference
+# rounded to fp16 is itself within 2^-11 = 4.9e-4 relative of the reference)
+FWD_TOL = {'f32': 2e-5, 'bf16': 2e-2, 'f16': 2.5e-3}
+SE_ACT = {'se_pre': 'relu', 'se_post': 'relu6'}
+# families that park the activated operand (backward: and the output gradient) in LDS at STORAGE precision; every other family
+# keeps what it loaded in fp32 registers (csrc/dwconv_fwd.hip, csrc/dwconv_bwd.hip: the At / Dt tiles are T)
+STAGED = ('LDS',)
+FAMILIES = ('TILE', 'ROW3', 'PLANE7', 'ROWK', 'LDS')
+
+
+def _route_of(backward, dt, gated, pooled, B, C, H, W, k, s):
     from torchdet3d import _native as N
-    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    return N.lib().t3d_dwconv_route(int(backward), {'f32': N.F32, 'bf16': N.BF16, 'f16': N.F16}[dt], int(gated), int(pooled), B, H, W, C, k, s)
+
+
+def _family_of(backward, dt, gated, pooled, B, C, H, W, k, s):
+    r = _route_of(backward, dt, gated, pooled, B, C, H, W, k, s)
+    assert r >= 0
+    from torchdet3d import _native as N
+    return {getattr(N, 'DW_' + f): f for f in FAMILIES}[r]
+
+
+@contextlib.contextmanager
+def _forced(c):
+    """The route a case names: forced when the row says so, asserted either way, DW_AUTO restored."""
+    from torchdet3d import _native as N
+    want = getattr(N, 'DW_' + c.family)
+    try:
+        if c.forced:
+            N.call('t3d_dwconv_force_route', want)
+        assert _route_of(c.direction == 'bwd', c.dtype, c.gated, c.pooled, c.B, c.C, c.H, c.W, c.k, c.stride) == want, c
+        yield
+    finally:
+        N.call('t3d_dwconv_force_route', N.DW_AUTO)
+
+
+def _check_fwd(B, C, H, W, k, s, dt, mode, act, staged, pooled=True, with_stats=True):
+    """One t3d_dwconv_fwd launch against torch-CPU F.conv2d on the pre-rounded operands: the stored output (every element
+    written), the statistics of the STORED values and the pooled sums, where requested.
+    mode: plain | bnact | se_pre | se_post; staged: the family keeps the activated operand at storage precision."""
+    from torchdet3d import _native as N
+    dtype = DTYPES[dt]
     g = torch.Generator().manual_seed(B * 1000 + C + k + s)
     x = torch.randn(B, C, H, W, generator=g)
     w = torch.randn(C, 1, k, k, generator=g) * 0.3
     scale = torch.rand(C, generator=g) + 0.5
     shift = torch.randn(C, generator=g) * 0.3
     se = torch.rand(B, C, generator=g)
-    act = {'plain': 'none', 'bnact': 'hswish', 'se_pre': 'relu', 'se_post': 'relu6'}[mode]
     xq = x.to(dtype).float()                      # what the kernel actually reads
     if mode == 'plain':
         a = xq
@@ -51,15 +90,15 @@ def test_dwconv_fwd(B, C, H, W, k, s, dt, mode):
             a = _act(u, act) * se.view(B, C, 1, 1)
         else:
             a = _act(u, act)
-    if dt == 'bf16':
+    if staged:
         a = a.to(dtype).float()                   # activated tile is parked in LDS in the storage dtype
     ref = F.conv2d(a, w, None, s, (k - 1) // 2, 1, C)
     Ho, Wo = ref.shape[2:]
     xd = _nhwc(x, dtype)
     wd = w.view(C, k * k).contiguous().cuda()
-    y = torch.empty(B, Ho, Wo, C, device='cuda', dtype=dtype)
-    stats = torch.zeros(2 * C, device='cuda', dtype=torch.float64)
-    gap = torch.zeros(B, C, device='cuda')
+    y = torch.full((B, Ho, Wo, C), float('nan'), device='cuda', dtype=dtype)       # sentinel: every element must be written
+    stats = torch.zeros(2 * C, device='cuda', dtype=torch.float64) if with_stats else None
+    gap = torch.zeros(B, C, device='cuda') if pooled else None
     keep = [t.cuda() for t in (scale, shift, se)]
     p = None
     if mode != 'plain':
@@ -68,14 +107,42 @@ def test_dwconv_fwd(B, C, H, W, k, s, dt, mode):
            B, H, W, C, k, s, N.stream())
     torch.cuda.synchronize()
     got = y.float().cpu().permute(0, 3, 1, 2)
-    tol = 2e-5 if dt == 'f32' else 2e-2
+    assert not torch.isnan(got).any(), 'part of the output was never written'
+    tol = FWD_TOL[dt]
     np.testing.assert_allclose(got.numpy(), ref.numpy(), atol=tol * max(1.0, ref.abs().max().item()), rtol=tol)
     # statistics are those of the STORED values
     n = B * Ho * Wo
-    st = stats.cpu().view(2, C)
-    np.testing.assert_allclose(st[0].numpy(), got.double().sum(dim=(0, 2, 3)).numpy(), rtol=1e-5, atol=1e-4 * n ** .5)
-    np.testing.assert_allclose(st[1].numpy(), (got.double() ** 2).sum(dim=(0, 2, 3)).numpy(), rtol=1e-5, atol=1e-4)
-    np.testing.assert_allclose(gap.cpu().numpy(), got.sum(dim=(2, 3)).numpy(), rtol=1e-4, atol=1e-3)
+    if with_stats:
+        st = stats.cpu().view(2, C)
+        np.testing.assert_allclose(st[0].numpy(), got.double().sum(dim=(0, 2, 3)).numpy(), rtol=1e-5, atol=1e-4 * n ** .5)
+        np.testing.assert_allclose(st[1].numpy(), (got.double() ** 2).sum(dim=(0, 2, 3)).numpy(), rtol=1e-5, atol=1e-4)
+    if pooled:
+        np.testing.assert_allclose(gap.cpu().numpy(), got.sum(dim=(2, 3)).numpy(), rtol=1e-4, atol=1e-3)
+
+
+@pytest.mark.parametrize('B,C,H,W,k,s', SHAPES)
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+@pytest.mark.parametrize('mode', ['plain', 'bnact', 'se_pre', 'se_post'])
+def test_dwconv_fwd(B, C, H, W, k, s, dt, mode):
+    """Whatever family the dispatcher picks for these shapes (always with pooled sums); the reference rounds the activated
+    operand of every bf16 case, which the 2e-2 margin covers for the families that keep it in fp32."""
+    act = {'plain': 'none', 'bnact': 'hswish', 'se_pre': 'relu', 'se_post': 'relu6'}[mode]
+    _check_fwd(B, C, H, W, k, s, dt, mode, act, staged=dt == 'bf16')
+
+
+def _case_ids(direction):
+    from dw_cases import CASES, case_id
+    rows = [c for c in CASES if c.direction == direction]
+    return dict(argvalues=rows, ids=[case_id(c) for c in rows])
+
+
+@pytest.mark.parametrize('c', **_case_ids('fwd'))
+def test_dwconv_fwd_of_the_family_the_case_names(c):
+    """tests/dw_cases.py: the row names its kernel family; the route is asserted in front of the launch."""
+    mode, _, act = c.mode.partition('-')
+    with _forced(c):
+        _check_fwd(c.B, c.C, c.H, c.W, c.k, c.stride, c.dtype, mode, act or SE_ACT.get(mode, 'none'), c.family in STAGED,
+                   pooled=bool(c.pooled), with_stats=c.stats)
 
 
 def test_bn_finalize_matches_batchnorm():
@@ -108,11 +175,9 @@ def test_bn_finalize_matches_batchnorm():
     np.testing.assert_allclose(got_e.numpy(), ref_e.numpy(), atol=2e-5)
 
 
-@pytest.mark.parametrize('B,C,H,W,k,s', SHAPES)
-@pytest.mark.parametrize('dt', ['f32', 'bf16'])
-@pytest.mark.parametrize('mode', ['plain_res', 'bnact', 'bnact_ps'])
-def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
-    """dx, dw and the BN-backward sums vs torch autograd of the same (pre-rounded) operands."""
+def _check_bwd(B, C, H, W, k, s, dt, mode, staged):
+    """One t3d_dwconv_bwd launch: dx, dw and the BN-backward sums vs torch autograd of the same (pre-rounded) operands.
+    staged: the family parks the activated input and dy in LDS at storage precision (a property of the family, not of k)."""
     from torchdet3d import _native as N
     dtype = torch.float32 if dt == 'f32' else torch.bfloat16
     q = lambda t: t.to(dtype).float()
@@ -120,13 +185,13 @@ def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
     x = torch.randn(B, C, H, W, generator=g)
     w = torch.randn(C, 1, k, k, generator=g) * 0.3
     scale, shift = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
-    act = 'hswish' if mode != 'plain_res' else 'none'
+    mode, _, act = mode.partition('-')      # bnact-<act>: bnact with another activation than hswish
+    act = 'none' if mode == 'plain_res' else act or 'hswish'
     xq = q(x)
     u = (xq * scale.view(1, C, 1, 1) + shift.view(1, C, 1, 1)) if mode != 'plain_res' else xq
     u = u.clone().requires_grad_(True)
     a1 = _act(u, act)
-    tiled = k != 3    # the tiled kernel (k=5) stages a and dy in LDS at storage precision; the 3x3 streaming kernels keep fp32
-    a1q = a1 + (q(a1) - a1).detach() if tiled else a1
+    a1q = a1 + (q(a1) - a1).detach() if staged else a1
     wr = w.clone().requires_grad_(True)
     yref = F.conv2d(a1q, wr, None, s, (k - 1) // 2, 1, C)
     Ho, Wo = yref.shape[2:]
@@ -136,7 +201,7 @@ def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
     alpha, gamma = torch.rand(shp, generator=g) + 0.5, torch.randn(shp, generator=g) * 0.1
     beta = torch.randn(1, C, 1, 1, generator=g) * 0.2
     dy = alpha * q(dz) + beta * q(y2) + gamma
-    yref.backward(q(dy) if tiled else dy)
+    yref.backward(q(dy) if staged else dy)
     res = torch.randn(B, C, H, W, generator=g)
     dx_ref = u.grad + (q(res) if mode == 'plain_res' else 0)
     d = lambda t: _nhwc(t, dtype)
@@ -145,7 +210,7 @@ def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
     bb = N.bnbwd(keep[0], keep[1], keep[2], ps)
     pro = None if mode == 'plain_res' else N.prologue(keep[3], keep[4], None, act, False)
     wd = w.view(C, k * k).contiguous().cuda()
-    dx = torch.empty(B, H, W, C, device='cuda', dtype=dtype)
+    dx = torch.full((B, H, W, C), float('nan'), device='cuda', dtype=dtype)      # sentinel: every element must be written
     stats = torch.zeros(2 * C, device='cuda', dtype=torch.float64)
     dw = torch.zeros(C, k * k, device='cuda')
     N.call('t3d_dwconv_bwd', N.dtype_code(xd), N.ptr(dzd), N.ptr(yd), bb, N.ptr(wd), N.ptr(xd), pro,
@@ -153,6 +218,7 @@ def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
            N.ptr(dw), B, H, W, C, k, s, N.stream())
     torch.cuda.synchronize()
     got = dx.float().cpu().permute(0, 3, 1, 2)
+    assert not torch.isnan(got).any(), 'part of the data gradient was never written'
     tol = 3e-5 if dt == 'f32' else 2e-2
     np.testing.assert_allclose(got.numpy(), dx_ref.numpy(), atol=tol * max(1., dx_ref.abs().max().item()), rtol=tol)
     tolw = 3e-5 if dt == 'f32' else 3e-3
@@ -164,6 +230,22 @@ def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
         np.testing.assert_allclose(st[0].numpy(), got.double().sum(dim=(0, 2, 3)).numpy(), rtol=1e-5, atol=1e-4 * n ** .5)
         np.testing.assert_allclose(st[1].numpy(), (got.double() * xq.double()).sum(dim=(0, 2, 3)).numpy(), rtol=1e-5,
                                    atol=1e-4 * n ** .5)
+
+
+@pytest.mark.parametrize('B,C,H,W,k,s', SHAPES)
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+@pytest.mark.parametrize('mode', ['plain_res', 'bnact', 'bnact_ps'])
+def test_dwconv_bwd(B, C, H, W, k, s, dt, mode):
+    """Whatever family the dispatcher picks for these shapes."""
+    _check_bwd(B, C, H, W, k, s, dt, mode, _family_of(1, dt, 0, 0, B, C, H, W, k, s) in STAGED)
+
+
+@pytest.mark.parametrize('c', **_case_ids('bwd'))
+def test_dwconv_bwd_of_the_family_the_case_names(c):
+    """tests/dw_cases.py: the row names its kernel family; the route is asserted in front of the launch.  The LDS-tiled
+    kernel (csrc/dwconv_bwd.hip), which every 3x3 backward of 2 GB and above falls to, has its reference check here."""
+    with _forced(c):
+        _check_bwd(c.B, c.C, c.H, c.W, c.k, c.stride, c.dtype, c.mode, c.family in STAGED)
 
 
 @pytest.mark.parametrize('B,C,H,W,k,s', [(8, 32, 56, 56, 3, 1), (4, 144, 28, 28, 3, 1), (4, 192, 28, 28, 3, 2), (2, 960, 7, 7, 3, 1),
@@ -279,6 +361,48 @@ def test_dwconv_bwd_refused_by_the_streaming_kernel_keeps_its_pending_finalize(s
     assert torch.allclose(res[False][5], res[True][5], rtol=1e-4, atol=1e-3)
 
 
+@pytest.mark.parametrize('s', [1, 2])
+def test_dw3_forward_of_a_2gb_tensor(s):
+    """At 2 GB and above the 3x3 row walk leaves its 32-bit buffer offsets: 64-bit pointers, and at stride 1 one column per
+    thread instead of two (dw3_fwd_kernel<T, 1, ...>) -- code no smaller tensor reaches.  bf16, 128 x 112 x 112 x 672 = 2.16 GB,
+    hswish prologue, no pooled sums; checked as test_gpu_production_shapes.py checks (its tolerances): eight channels over the
+    whole batch in fp64 on the CPU (output and statistics), and every channel of the first and of the last image -- byte
+    2^31 of the input lies inside image 127 (126.97 images in)."""
+    from torchdet3d import _native as N
+    from test_gpu_production_shapes import _nchw64, _sel
+    B, H, W, C = 128, 112, 112, 672
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    assert B * H * W * C * 2 >= 1 << 31 > (B - 1) * H * W * C * 2
+    assert _family_of(0, 'bf16', 0, 0, B, C, H, W, 3, s) == 'ROW3'
+    gd = torch.Generator(device='cuda').manual_seed(7 + s)
+    x = torch.randn(B * H * W, C, device='cuda', generator=gd).to(torch.bfloat16).view(B, H, W, C)
+    g = torch.Generator().manual_seed(70 + s)
+    w = torch.randn(C, 9, generator=g) * 0.3
+    scale, shift = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
+    y = torch.full((B, Ho, Wo, C), float('nan'), device='cuda', dtype=torch.bfloat16)
+    stats = torch.zeros(2 * C, device='cuda', dtype=torch.float64)
+    wd, sc, sh = w.cuda(), scale.cuda(), shift.cuda()
+    pro = N.prologue(sc, sh, None, 'hswish', False)
+    N.call('t3d_dwconv_fwd', N.BF16, N.ptr(x), pro, N.ptr(wd), N.ptr(y), N.ptr(stats), None, B, H, W, C, 3, s, N.stream())
+    torch.cuda.synchronize()
+    assert not torch.isnan(y).any().item(), 'part of the output was never written'
+
+    def ref_of(xs, ch):
+        u = xs * scale[ch].double().view(1, -1, 1, 1) + shift[ch].double().view(1, -1, 1, 1)
+        return F.conv2d(u * (u + 3).clamp(0, 6) / 6, w[ch].double().view(-1, 1, 3, 3), None, s, 1, 1, len(ch))
+    sel = _sel(C)
+    ref, got = ref_of(_nchw64(x, sel), sel), _nchw64(y, sel)
+    # stored bf16 output: 2^-8 relative + the fp32 9-tap accumulation
+    np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=8e-3, atol=8e-3 * ref.abs().max().item())
+    st = stats.cpu().view(2, C)[:, sel]
+    np.testing.assert_allclose(st[0].numpy(), got.sum(dim=(0, 2, 3)).numpy(), rtol=1e-5, atol=1e-5 * got.abs().sum().item() / len(sel))
+    np.testing.assert_allclose(st[1].numpy(), (got ** 2).sum(dim=(0, 2, 3)).numpy(), rtol=1e-5)
+    every = torch.arange(C)
+    for b in (0, B - 1):
+        ref, got = ref_of(_nchw64(x[b:b + 1], every), every), _nchw64(y[b:b + 1], every)
+        np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=8e-3, atol=8e-3 * ref.abs().max().item())
+
+
 @pytest.mark.parametrize('B,C,H,W,k,s', [(2, 32, 24, 24, 3, 1), (2, 96, 24, 24, 3, 2), (5, 264, 9, 7, 3, 1), (3, 40, 13, 17, 3, 2), (2, 960, 7, 7, 3, 1)])
 @pytest.mark.parametrize('dt', ['f32', 'bf16'])
 def test_3x3_register_tiles_opt_in(B, C, H, W, k, s, dt):
@@ -288,9 +412,10 @@ def test_3x3_register_tiles_opt_in(B, C, H, W, k, s, dt):
     from torchdet3d import _native as N
     N.call('t3d_dwconv_force_route', N.DW_TILE)
     try:
-        test_dwconv_fwd(B, C, H, W, k, s, dt, 'bnact')
-        test_dwconv_bwd(B, C, H, W, k, s, dt, 'bnact_ps')
-        test_dwconv_bwd(B, C, H, W, k, s, dt, 'plain_res')
+        assert _family_of(0, dt, 0, 1, B, C, H, W, k, s) == 'TILE' and _family_of(1, dt, 0, 0, B, C, H, W, k, s) == 'TILE'
+        _check_fwd(B, C, H, W, k, s, dt, 'bnact', 'hswish', staged=dt == 'bf16')
+        _check_bwd(B, C, H, W, k, s, dt, 'bnact_ps', 'TILE' in STAGED)
+        _check_bwd(B, C, H, W, k, s, dt, 'plain_res', 'TILE' in STAGED)
     finally:
         N.call('t3d_dwconv_force_route', N.DW_AUTO)
 
