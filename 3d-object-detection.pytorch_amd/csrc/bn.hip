@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(const T3dFold* __restrict_
   __shared__ float sink[3 * 64];
   const int C = fp->C, cbase = blockIdx.x * 64;
   if (cbase >= C) return;
-  t3d_fold_block(fp, cbase, min(64, C - cbase), sink, 64, true);
+  t3d_fold_block<0>(fp, cbase, min(64, C - cbase), sink, 64, true);
 }
 
 }  // namespace

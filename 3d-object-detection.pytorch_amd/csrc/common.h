@@ -125,96 +125,146 @@ inline const T3dFold* t3d_take_fold(const void* key) {
 int t3d_fold_fallback(const void* key, hipStream_t st);
 
 // Whole workgroup: channels [cbase, cbase + Cb) -> dst[0 .. Cb) = o0, dst[ld .. ld + Cb) = o1, dst[2 ld ..) = o2 (kind 2);
-// ends with a barrier.  One thread per channel (consecutive threads = consecutive channels: coalesced 8-B loads), U
-// channels per thread at once when the replica count leaves registers for it; every replica load is issued before the
-// first add (the sums were written by device-scope atomics and live at the memory side, ~2 us away: a loop with a
-// data-dependent trip count would make one round trip per iteration).  `between` runs once per thread between the issue
-// of the first batch of loads and their use -- work that does not need the coefficients (weight staging) hides the round
-// trip.  `publish`: this workgroup is the one that writes the channels' finalize outputs.
+// ends with a barrier.  KIND: the descriptor's kind, known at every call site (1 forward, 2 backward coefficients; 0: read
+// it from the descriptor -- the standalone fold launch, bn.hip) -- one of the two arithmetic paths is compiled per kernel.
+// One thread per channel (consecutive threads = consecutive channels: coalesced 8-B loads), U channels per thread at
+// once when the replica count leaves registers for it; every replica load is issued before the first add (the sums were
+// written by device-scope atomics and live at the memory side, ~2 us away: a loop with a data-dependent trip count
+// would make one round trip per iteration), and the per-channel parameters the arithmetic needs (gamma / beta, or the
+// forward's mean / invstd) are fetched WITH the sums, not behind them.  A WAVE whose 64 channel slots all lie at or
+// beyond Cb (16 .. 96 channels occupy one or two waves of an 8-wave block) reads neither the descriptor nor the sums and
+// runs none of the fp64 path: it goes to `between` and the closing barrier, and leaves its SIMD to the waves that have
+// channels.  `between` runs once per thread between the issue of the first batch of loads and their use -- work that
+// does not need the coefficients (weight staging) hides the round trip.  `publish`: this workgroup is the one that
+// writes the channels' finalize outputs (the only reader of the descriptor's output fields).
+// The arithmetic per channel -- replica sums added in index order from 0.0, then bn.hip's expressions -- is the same
+// whichever body runs (a surplus replica slot adds 0.0, which is exact).
+// T3D_FOLD_STAMP(i): empty, unless a unit defines it in front of this header (the -DT3D_PW_TRACE build of pwconv_stream.hip,
+// tools/pw_trace.sh): 0 descriptor read, 1 sums arrived (and `between` done), 2 coefficients in LDS.
+#ifndef T3D_FOLD_STAMP
+#define T3D_FOLD_STAMP(i)
+#endif
 struct T3dNoop { __device__ __forceinline__ void operator()() const {} };
-template <class Between = T3dNoop>
+template <int KIND, class Between = T3dNoop>
 __device__ __forceinline__ void t3d_fold_block(const T3dFold* __restrict__ fp, int cbase, int Cb, float* dst, int ld,
                                                bool publish, Between between = Between()) {
-  const T3dFold f = *fp;
-  const int nthr = blockDim.x;
-  auto finish = [&](int i, double s1, double s2) {
-    const int c = cbase + i;
-    if (f.kind == 1) {
-      const double mean = s1 / f.count;
-      double var = s2 / f.count - mean * mean;  // biased
-      if (var < 0.0) var = 0.0;
-      const float invstd = (float)(1.0 / sqrt(var + (double)f.eps));
-      const float g = f.gamma ? f.gamma[c] : 1.f, b = f.beta ? f.beta[c] : 0.f;
-      const float sc = g * invstd, sh = b - (float)mean * sc;
-      dst[i] = sc;
-      dst[ld + i] = sh;
-      if (publish) {
-        f.o0[c] = sc;
-        f.o1[c] = sh;
-        if (f.o2) f.o2[c] = (float)mean;
-        if (f.o3) f.o3[c] = invstd;
-        if (f.rm) f.rm[c] = (1.f - f.momentum) * f.rm[c] + f.momentum * (float)mean;
-        if (f.rv) {
-          const double unbiased = f.count > 1.0 ? var * f.count / (f.count - 1.0) : var;
-          f.rv[c] = (1.f - f.momentum) * f.rv[c] + f.momentum * (float)unbiased;
-        }
-        if (c == 0 && f.nbt) *f.nbt += 1;
-      }
-    } else {
-      const double mu = (double)f.mean[c], is = (double)f.invstd[c];
-      const double dg = is * (s2 - mu * s1);
-      const double al = (double)(f.gamma ? f.gamma[c] : 1.f) * is;
-      const double be = -al * is * dg / f.count;
-      const float ga = (float)(-al * s1 / f.count - be * mu);
-      dst[i] = (float)al;
-      dst[ld + i] = (float)be;
-      dst[2 * ld + i] = ga;
-      if (publish) {
-        f.o0[c] = (float)al;
-        f.o1[c] = (float)be;
-        f.o2[c] = ga;
-        if (f.o3) f.o3[c] = (float)dg;
-        if (f.o4) f.o4[c] = (float)s1;
-      }
+  if constexpr (KIND == 0) {
+    if (fp->kind == 1) t3d_fold_block<1>(fp, cbase, Cb, dst, ld, publish, between);
+    else t3d_fold_block<2>(fp, cbase, Cb, dst, ld, publish, between);
+  } else {
+    const int nthr = blockDim.x, lane = threadIdx.x & 63;
+    const int wbase = __builtin_amdgcn_readfirstlane((int)threadIdx.x - lane);   // the wave's first channel slot (scalar)
+    const bool live = wbase < Cb;
+    // what addresses the sums and enters the arithmetic; the publishing fields stay in memory until the publish branch
+    int nrep = 16, C = 0;
+    long long rstride = 0;
+    const double* stats = nullptr;
+    double count = 1.0;
+    float eps = 0.f;
+    const float *pa = nullptr, *pb = nullptr, *pc = nullptr;   // kind 1: gamma, beta | kind 2: mean, invstd, gamma
+    if (live) {
+      nrep = fp->nrep; C = fp->C; rstride = fp->rstride; stats = fp->stats; count = fp->count;
+      if (KIND == 1) { eps = fp->eps; pa = fp->gamma; pb = fp->beta; }
+      else { pa = fp->mean; pb = fp->invstd; pc = fp->gamma; }
     }
-  };
-  auto pass = [&](auto nr_tag, auto u_tag) {
-    constexpr int NR = decltype(nr_tag)::value, U = decltype(u_tag)::value;
-    bool first = true;
-    for (int i0 = threadIdx.x; i0 < Cb || first; i0 += U * nthr) {      // (every thread runs the first round: `between`)
-      double v1[U][NR], v2[U][NR];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = min(i0 + u * nthr, Cb - 1);          // clamped: the surplus lanes' results are never used
-        const double* p = f.stats + cbase + i;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const size_t o = (size_t)min(r, f.nrep - 1) * f.rstride;
-          v1[u][r] = p[o];
-          v2[u][r] = p[o + f.C];
+    T3D_FOLD_STAMP(0);
+    auto finish = [&](int i, double s1, double s2, float xa, float xb, float xc) {
+      const int c = cbase + i;
+      if (KIND == 1) {
+        const double mean = s1 / count;
+        double var = s2 / count - mean * mean;  // biased
+        if (var < 0.0) var = 0.0;
+        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float g = xa, b = xb;
+        const float sc = g * invstd, sh = b - (float)mean * sc;
+        dst[i] = sc;
+        dst[ld + i] = sh;
+        if (publish) {
+          float* const o2 = fp->o2; float* const o3 = fp->o3; float* const rm = fp->rm; float* const rv = fp->rv;
+          const float momentum = fp->momentum;
+          fp->o0[c] = sc;
+          fp->o1[c] = sh;
+          if (o2) o2[c] = (float)mean;
+          if (o3) o3[c] = invstd;
+          if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mean;
+          if (rv) {
+            const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+            rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unbiased;
+          }
+          if (c == 0 && fp->nbt) *fp->nbt += 1;
+        }
+      } else {
+        const double mu = (double)xa, is = (double)xb;
+        const double dg = is * (s2 - mu * s1);
+        const double al = (double)xc * is;
+        const double be = -al * is * dg / count;
+        const float ga = (float)(-al * s1 / count - be * mu);
+        dst[i] = (float)al;
+        dst[ld + i] = (float)be;
+        dst[2 * ld + i] = ga;
+        if (publish) {
+          float* const o3 = fp->o3; float* const o4 = fp->o4;
+          fp->o0[c] = (float)al;
+          fp->o1[c] = (float)be;
+          fp->o2[c] = ga;
+          if (o3) o3[c] = (float)dg;
+          if (o4) o4[c] = (float)s1;
         }
       }
-      if (first) {
-        between();
-        first = false;
-      }
+    };
+    auto pass = [&](auto nr_tag, auto u_tag) {
+      constexpr int NR = decltype(nr_tag)::value, U = decltype(u_tag)::value;
+      bool first = true;
+      for (int w0 = wbase; w0 < Cb || first; w0 += U * nthr) {      // (every thread runs the first round: `between`)
+        const int i0 = w0 + lane;
+        double v1[U][NR], v2[U][NR];
+        float xa[U], xb[U], xc[U];
+        if (w0 < Cb) {                                       // wave-uniform
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        double s1 = 0.0, s2 = 0.0;
+          for (int u = 0; u < U; ++u) {
+            const int i = min(i0 + u * nthr, Cb - 1);          // clamped: the surplus lanes' results are never used
+            const double* p = stats + cbase + i;
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          s1 += r < f.nrep ? v1[u][r] : 0.0;
-          s2 += r < f.nrep ? v2[u][r] : 0.0;
+            for (int r = 0; r < NR; ++r) {
+              const size_t o = (size_t)min(r, nrep - 1) * rstride;
+              v1[u][r] = p[o];
+              v2[u][r] = p[o + C];
+            }
+            if (KIND == 1) {
+              xa[u] = pa ? pa[cbase + i] : 1.f;
+              xb[u] = pb ? pb[cbase + i] : 0.f;
+              xc[u] = 0.f;
+            } else {
+              xa[u] = pa[cbase + i];
+              xb[u] = pb[cbase + i];
+              xc[u] = pc ? pc[cbase + i] : 1.f;
+            }
+          }
         }
-        if (i0 + u * nthr < Cb) finish(i0 + u * nthr, s1, s2);
+        if (first) {
+          between();
+          first = false;
+          T3D_FOLD_STAMP(1);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (w0 + u * nthr >= Cb) continue;                // wave-uniform: none of the wave's slots of this batch is a channel
+          double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+          for (int r = 0; r < NR; ++r) {
+            s1 += r < nrep ? v1[u][r] : 0.0;
+            s2 += r < nrep ? v2[u][r] : 0.0;
+          }
+          if (i0 + u * nthr < Cb) finish(i0 + u * nthr, s1, s2, xa[u], xb[u], xc[u]);
+        }
       }
-    }
-  };
-  if (f.nrep <= 2) pass(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{});
-  else if (f.nrep <= 4) pass(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
-  else if (f.nrep <= 8) pass(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
-  else pass(std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{});
-  __syncthreads();
+    };
+    if (nrep <= 4) pass(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
+    else if (nrep <= 8) pass(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
+    else pass(std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{});
+    T3D_FOLD_STAMP(2);
+    __syncthreads();
+  }
 }
 
 // ---- order-independent BatchNorm sums (forward) ------------------------------------------------------------------

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(NTH) T3D_DWB_OCC void dw3_bwd2_kernel(const Dw3BArg
   // requested BatchNorm-backward finalize of the gradient's coefficients (alpha, beta, gamma), derived here (common.h):
   // the block's own channel range into the scratch behind the weights; one block per channel range publishes
   float* fco = lred + 9 * Cb;           // [3][Cb]
-  if (a.fold) t3d_fold_block(a.fold, cbase, Cb, fco, Cb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0));
+  if (a.fold) t3d_fold_block<2>(a.fold, cbase, Cb, fco, Cb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0));
   f32x2 sc2[H2], sh2[H2], al2[H2], be2[H2], ga2[H2];
   f32x2 wacc[9][H2];
   float psum[CH], psq[CH];
@@ -629,7 +629,7 @@ __global__ __launch_bounds__(NTH) void dw3_bwd_s2_kernel(const Dw3BArgs a) {
   const int cbase = a.slab ? blockIdx.y * 64 * CH : 0;
   const int Cb = a.slab ? min(64 * CH, a.C - cbase) : a.C;
   // requested BatchNorm-backward finalize of the gradient's coefficients, derived here (see dw3_bwd2_kernel)
-  if (a.fold) t3d_fold_block(a.fold, cbase, Cb, lred, Cb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0));
+  if (a.fold) t3d_fold_block<2>(a.fold, cbase, Cb, lred, Cb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0));
 
   f32x2 sc2[H2], sh2[H2], al2[H2], be2[H2], ga2[H2];
   f32x2 wt[9][H2], wacc[9][H2];

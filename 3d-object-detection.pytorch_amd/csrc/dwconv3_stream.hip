@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void dw3_fwd_kernel(const Dw3Args a) {
   // the producer's BatchNorm finalize, derived here when requested (common.h): the block's own channel range through
   // the statistics scratch (free until the end of the kernel); one block per channel range publishes
   const int fbase = a.slab ? blockIdx.y * 64 * CH : 0, fCb = a.slab ? min(64 * CH, a.C - fbase) : a.C;
-  if (a.fold) t3d_fold_block(a.fold, fbase, fCb, lstat, fCb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0));
+  if (a.fold) t3d_fold_block<1>(a.fold, fbase, fCb, lstat, fCb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0));
 
   float wt[9][CH], sc[CH], sh[CH], psum[CH], psq[CH];
   {
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void dw3_fwd2_kernel(const Dw3Args a) {
       }
     };
     // (the stencil weights are fetched while the sums of a derived finalize are in flight)
-    if (a.fold) t3d_fold_block(a.fold, fbase, fCb, lstat, fCb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0), load_w);
+    if (a.fold) t3d_fold_block<1>(a.fold, fbase, fCb, lstat, fCb, a.slab ? blockIdx.x == 0 : (blockIdx.x == 0 && blockIdx.y == 0), load_w);
     else load_w();
 #pragma unroll
     for (int h = 0; h < H2; ++h) {

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const EwArgs a) {
   const size_t nthr = ((size_t)gridDim.x * 256 / CG) * CG;
   const size_t g = blockIdx.x * (size_t)256 + threadIdx.x;
   extern __shared__ float fco[];     // [2][C], only with a requested finalize (common.h): derived here, block 0 publishes
-  if (a.fold) t3d_fold_block(a.fold, 0, a.C, fco, a.C, blockIdx.x == 0);
+  if (a.fold) t3d_fold_block<1>(a.fold, 0, a.C, fco, a.C, blockIdx.x == 0);
   if (g >= nthr) return;
   const int c0 = (int)(g % CG) * 8;
   float sc[8], sh[8];

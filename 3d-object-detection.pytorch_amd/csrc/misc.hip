@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void se_bwd_affine_fold_kernel(const float* __
   const int c0 = blockIdx.x * 32, cb = min(32, C - c0);
   // blockIdx.y: a chunk of samples (the derive is repeated per chunk -- 32 channels x the replicas, a few hundred bytes; chunk 0
   // publishes).  One workgroup per channel block walking all samples was a 17-us latency chain on 30 CUs.
-  t3d_fold_block(fold, c0, cb, &co[0][0], 32, blockIdx.y == 0);      // (ends with a barrier)
+  t3d_fold_block<2>(fold, c0, cb, &co[0][0], 32, blockIdx.y == 0);      // (ends with a barrier)
   const int per = (B + gridDim.y - 1) / gridDim.y, b0 = blockIdx.y * per, b1 = min(B, b0 + per);
   for (int i = b0 * 32 + threadIdx.x; i < b1 * 32; i += 256) {
     const int b = i >> 5, cl = i & 31;

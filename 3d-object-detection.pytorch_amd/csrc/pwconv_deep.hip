@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64 * NW) void pw_deep_kernel(const GemmArgs a, cons
     for (int i = a.Kin + tid; i < kpad; i += 64 * NW) {
       coef[i] = DG ? 0.f : 1.f; coef[kpad + i] = 0.f; coef[2 * kpad + i] = 0.f;
     }
-    t3d_fold_block(a.fold, 0, a.Kin, coef, kpad, blockIdx.x == 0 && blockIdx.y == 0);
+    t3d_fold_block<DG ? 2 : 1>(a.fold, 0, a.Kin, coef, kpad, blockIdx.x == 0 && blockIdx.y == 0);
   } else {
     for (int i = tid; i < kpad; i += 64 * NW) {
       const bool v = i < a.Kin;

@@ -20,6 +20,19 @@
 // flight), not by a block-wide pipeline.
 #include <cstdlib>
 #include <type_traits>
+#ifdef T3D_PW_TRACE
+// debug build only (tools/pw_trace.sh): wall-clock stamps (10 ns units) of the first and the last block's wave 0; slots 0-4 the
+// kernel's phases (PW_STAMP below), 5-7 the BatchNorm derive of its prologue (T3D_FOLD_STAMP, common.h) -- each of those first
+// waits for everything the wave has in flight, so that the stamp says "arrived", not "issued"
+#include <hip/hip_runtime.h>
+static __device__ unsigned long long g_pw_trace[16];
+#define T3D_FOLD_STAMP(i)                                                                                 \
+  do {                                                                                                    \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                           \
+    if (threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))                            \
+      g_pw_trace[(blockIdx.x == 0 ? 0 : 8) + 5 + (i)] = wall_clock64();                                   \
+  } while (0)
+#endif
 #include "pwconv_route.h"
 
 // Storage type of this translation unit.  The file is compiled twice: as it stands for bf16 (training + inference, every
@@ -56,9 +69,7 @@ namespace {
 // YF (with DG): y-free data gradient -- the main loop is the plain forward loop over two raw tensors ([dz | x], no
 // transform), the epilogue is the data gradient's (activation derivative, residual, BatchNorm-backward sums).
 #ifdef T3D_PW_TRACE
-// debug build only (tools/pw_trace.sh): wall-clock stamps (10 ns units) of the first and the last block's wave 0
-__device__ unsigned long long g_pw_trace[16];
-#define PW_STAMP(i)                                                                                       \
+#define PW_STAMP(i)                                                                                     \
   do {                                                                                                    \
     if (threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))                            \
       g_pw_trace[(blockIdx.x == 0 ? 0 : 8) + (i)] = wall_clock64();                                       \
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(512, KU > 2 ? 1 : 2) void pw_stream_kernel(const Ge
       coef[i] = DG ? 0.f : 1.f; coef[kpad + i] = 0.f; coef[2 * kpad + i] = 0.f;
     }
     // (the weight staging runs between the issue of the sums' loads and their use: one round trip instead of two)
-    t3d_fold_block(a.fold, 0, a.Kin, coef, kpad, blockIdx.x == 0, stage_weights);
+    t3d_fold_block<DG ? 2 : 1>(a.fold, 0, a.Kin, coef, kpad, blockIdx.x == 0, stage_weights);
   } else {
   stage_weights();
   for (int i = tid; i < kpad; i += nthr) {
@@ -556,13 +567,19 @@ __global__ __launch_bounds__(512, KU > 2 ? 1 : 2) void pw_stream_kernel(const Ge
 #pragma unroll
     for (int q = 0; q < NT / 2; ++q) {
       const int n = nb + 32 * q;
+      // row16_sum leaves the SAME bits in all 16 lanes of a row (every level adds the same two values in either order), so
+      // lane lc keeps result lc of the group's 16 -- sum j = lc & 7 of (lc < 8 ? st1 : st2) -- and the block's 64 sums of this
+      // 32-channel block go into LDS as ONE fp64 atomic with every lane active (it was 16, each with the four lc == 0 lanes
+      // active, behind 16 snaps); the values added are the same values
+      float mine = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float s1 = row16_sum(st1[q][j]), s2 = row16_sum(st2[q][j]);
-        if (lc == 0 && n < a.Nout) {
-          atomicAdd(dstat + (n - n0 + j) * 2, t3d_snap(s1, a.quant, false));
-          atomicAdd(dstat + (n - n0 + j) * 2 + 1, t3d_snap(s2, a.quant, !DG));
-        }
+        mine = lc == j ? s1 : (lc == j + 8 ? s2 : mine);
+      }
+      if (n < a.Nout) {
+        const double d = lc < 8 ? t3d_snap(mine, a.quant, false) : t3d_snap(mine, a.quant, !DG);
+        atomicAdd(dstat + (n - n0 + (lc & 7)) * 2 + (lc >> 3), d);
       }
     }
     __syncthreads();

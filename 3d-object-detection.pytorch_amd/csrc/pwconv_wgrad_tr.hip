@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
   if (!YF && a.fold) {
     const int nv = min(dyB, a.N - dy0);
     for (int i = nv + threadIdx.x; i < dyB; i += 256 * G) cdy[i] = cdy[dyB + i] = cdy[2 * dyB + i] = 0.f;
-    t3d_fold_block(a.fold, dy0, nv, cdy, dyB, false);
+    t3d_fold_block<2>(a.fold, dy0, nv, cdy, dyB, false);
   } else {
   for (int i = threadIdx.x; i < dyB && !YF; i += 256 * G) {
     const int n = dy0 + i;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256 * G) void pw_wgrad_tr_kernel(const WgtArgs a) {
       float* fco = cdy;                              // [3][dyB] (free in the y-free layout): alpha, beta, gamma of the expansion's BN
       if (a.fold) {
         for (int i = Nz + threadIdx.x; i < dyB; i += 256 * G) fco[i] = fco[dyB + i] = fco[2 * dyB + i] = 0.f;
-        t3d_fold_block(a.fold, 0, Nz, fco, dyB, blockIdx.x == 0);
+        t3d_fold_block<2>(a.fold, 0, Nz, fco, dyB, blockIdx.x == 0);
       } else {
         for (int i = threadIdx.x; i < dyB; i += 256 * G) {
           const bool v = i < Nz;

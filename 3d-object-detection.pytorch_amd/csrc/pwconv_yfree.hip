@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void yfree_prep_kernel(const bf16_t* __restric
   __shared__ f32x4 red[3][64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lg = lane >> 4, lc = lane & 15;
   if (fold) {
-    t3d_fold_block(fold, 0, N, fco, N, blockIdx.x == 0 && blockIdx.y == 0);     // (ends with a barrier)
+    t3d_fold_block<2>(fold, 0, N, fco, N, blockIdx.x == 0 && blockIdx.y == 0);     // (ends with a barrier)
   } else {
     for (int i = t; i < N; i += 256) { fco[i] = alpha_g[i]; fco[N + i] = beta_g[i]; fco[2 * N + i] = gamma_g[i]; }
     __syncthreads();

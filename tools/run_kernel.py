@@ -107,6 +107,28 @@ else:
         dw = torch.zeros(Nn, K, device=dev)
         fn = lambda: N.call('t3d_pwconv_wgrad', N.dtype_code(x), N.ptr(dz), N.ptr(yy), bb, N.ptr(x), pro, N.ptr(dw),
                             M, HW, K, Nn, N.stream())
+if '--fold' in sys.argv:
+    # pwfwd / pwdgrad: every launch serves a BatchNorm finalize request for the coefficients of its operand (t3d_fold_request,
+    # include/t3d.h) -- the derive prologue of csrc/common.h runs, as it does in the training step; sums in --nrep replicas
+    assert kind in ('pwfwd', 'pwdgrad')
+    Cf = K if kind == 'pwfwd' else Nn
+    fst = torch.randn(nrep, 2 * Cf, device=dev, dtype=torch.float64)
+    fst[:, Cf:] = fst[:, Cf:].abs() * M + fst[:, :Cf] ** 2            # (kind 1: a positive variance)
+    fo = [torch.empty(Cf, device=dev) for _ in range(5)]
+    fmean, fis, fg = rnd(Cf) * 0.1, torch.rand(Cf, device=dev) + 0.5, torch.rand(Cf, device=dev) + 0.5
+    f = N.BnFold()
+    f.kind, f.C, f.nrep, f.rstride, f.count, f.eps, f.momentum = (1 if kind == 'pwfwd' else 2), Cf, nrep, 2 * Cf, float(M), 1e-5, 0.1
+    f.stats, f.gamma, f.beta, f.mean, f.invstd = N.ptr(fst), N.ptr(fg), N.ptr(fmean), N.ptr(fmean), N.ptr(fis)
+    key = sc if kind == 'pwfwd' else al
+    f.o0, f.o1 = N.ptr(key), N.ptr(sh if kind == 'pwfwd' else be)
+    f.o2, f.o3, f.o4 = (N.ptr(fo[2]), N.ptr(fo[3]), N.ptr(fo[4])) if kind == 'pwfwd' else (N.ptr(ga), N.ptr(fo[3]), N.ptr(fo[4]))
+    fdesc = torch.frombuffer(bytearray(bytes(f)), dtype=torch.uint8).to(dev)
+    plain = fn
+
+    def fn():
+        N.call('t3d_fold_request', N.ptr(fdesc), N.ptr(key))
+        plain()
+        assert not N.lib().t3d_fold_pending()
 fn(); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
@@ -135,3 +157,6 @@ if os.environ.get('T3D_TRACE'):      # library built with -DT3D_PW_TRACE (tools/
     for nm, o in (('first block', 0), ('last block', 8)):
         print(f'  {nm}: start {t[o] - base:.2f} | weights staged {t[o + 1] - base:.2f} | first k-loop done {t[o + 2] - base:.2f} | '
               f'groups done {t[o + 3] - base:.2f} | stats done {t[o + 4] - base:.2f}')
+        if '--fold' in sys.argv:      # the derive inside "weights staged" (T3D_FOLD_STAMP, csrc/common.h); the barrier behind it is that stamp
+            print(f'  {nm} derive: descriptor read {t[o + 5] - base:.2f} | sums arrived, weights staged {t[o + 6] - base:.2f} | '
+                  f'coefficients in LDS {t[o + 7] - base:.2f} | barrier passed {t[o + 1] - base:.2f}')
