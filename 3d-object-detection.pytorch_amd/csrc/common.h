@@ -40,9 +40,9 @@ struct T3dReduceCfg {
 extern T3dReduceCfg g_t3d_reduce;
 
 // Environment switches on launch paths are read ONCE per process (getenv walks the whole environment block): a
-// lambda per use site holds its own static -- T3D_NO_SNAP (plain BatchNorm sums) and T3D_SE_GROUP (the one-launch
-// squeeze-excite group kernels).  (Which kernel family a convolution takes is steered by a call, not the environment:
-// t3d_dwconv_force_route, t3d_pwconv_force_route.)
+// lambda per use site holds its own static.  T3D_NO_SNAP (plain BatchNorm sums, a numerics diagnostic) is the only one.
+// (Which kernel family a convolution takes is steered by a call, not the environment: t3d_dwconv_force_route,
+// t3d_pwconv_force_route.)
 #define T3D_ENV_SET(name) ([]() -> bool { static const bool v = getenv(name) != nullptr; return v; }())
 
 // Kernel-exact timing of the NEXT depthwise launch (t3d_set_launch_events, misc.hip): the two events are attached to the

@@ -585,8 +585,3 @@ extern "C" int t3d_pool_bwd(int dtype, const float* dpooled, const void* y, cons
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
-
-extern "C" int t3d_gap_bwd(int dtype, const float* dpooled, const void* y, const t3d_prologue* pro, void* dz,
-                           double* stats, int B, int HW, int C, void* stream) {
-  return t3d_pool_bwd(dtype, dpooled, y, pro, T3D_POOL_AVG, nullptr, dz, stats, B, HW, C, stream);
-}

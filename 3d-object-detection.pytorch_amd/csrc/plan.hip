@@ -64,7 +64,7 @@ struct Entry { const char* name; int (*run)(const uint64_t*); int nargs; };
 // every entry point a step can contain (queries that return sizes / flags are not enqueue calls and are not listed)
 const Entry kEntries[] = {
     T3D_E(t3d_dwconv_fwd), T3D_E(t3d_bn_finalize), T3D_E(t3d_bn_eval_affine), T3D_E(t3d_bn_eval_affine_batched),
-    T3D_E(t3d_pwconv_fwd), T3D_E(t3d_pwconv_dgrad), T3D_E(t3d_pack_weight), T3D_E(t3d_sum_replicas_batched),
+    T3D_E(t3d_pwconv_fwd), T3D_E(t3d_pwconv_dgrad), T3D_E(t3d_pack_weight),
     T3D_E(t3d_set_dw_slots), T3D_E(t3d_set_exact_pool), T3D_E(t3d_sum_slots_batched), T3D_E(t3d_dwconv_bwd),
     T3D_E(t3d_pwconv_wgrad), T3D_E(t3d_pwconv_yfree_prep), T3D_E(t3d_pwconv_dgrad_yfree), T3D_E(t3d_pwconv_wgrad_yfree),
     T3D_E(t3d_pwconv_yfree_prep2), T3D_E(t3d_pwconv_bwd_yfree), T3D_E(t3d_pwconv_bwd_yfree_w), T3D_E(t3d_pwconv_wgrad_yfree_finish),
@@ -72,9 +72,9 @@ const Entry kEntries[] = {
     T3D_E(t3d_pwconv_fwd_mat), T3D_E(t3d_im2col), T3D_E(t3d_im2col_nchw), T3D_E(t3d_col2im_bwd), T3D_E(t3d_pack_conv_weight),
     T3D_E(t3d_unpack_conv_grad), T3D_E(t3d_maxpool_fwd), T3D_E(t3d_maxpool_bwd), T3D_E(t3d_res_relu_fwd),
     T3D_E(t3d_res_relu_bwd), T3D_E(t3d_subsample), T3D_E(t3d_ir_block_eval), T3D_E(t3d_bn_apply), T3D_E(t3d_bn_act_bwd),
-    T3D_E(t3d_gap_fwd), T3D_E(t3d_gap_bwd), T3D_E(t3d_pool_fwd), T3D_E(t3d_pool_bwd), T3D_E(t3d_head_fwd),
-    T3D_E(t3d_linear_fwd), T3D_E(t3d_head_fwd_all), T3D_E(t3d_head_bwd), T3D_E(t3d_head_bwd_weights), T3D_E(t3d_se_fwd),
-    T3D_E(t3d_se_bwd), T3D_E(t3d_se_fwd_fused), T3D_E(t3d_se_bwd_data), T3D_E(t3d_se_bwd_weights), T3D_E(t3d_se_after_sums),
+    T3D_E(t3d_gap_fwd), T3D_E(t3d_pool_fwd), T3D_E(t3d_pool_bwd), T3D_E(t3d_head_fwd),
+    T3D_E(t3d_linear_fwd), T3D_E(t3d_head_fwd_all), T3D_E(t3d_head_bwd), T3D_E(t3d_head_bwd_weights),
+    T3D_E(t3d_se_fwd_fused), T3D_E(t3d_se_bwd_data), T3D_E(t3d_se_bwd_weights), T3D_E(t3d_se_after_sums),
     T3D_E(t3d_se_after_apply), T3D_E(t3d_se_after_bwd), T3D_E(t3d_set_reduction_replicas), T3D_E(t3d_set_workspace), T3D_E(t3d_set_main_workspace),
     T3D_E(t3d_fold_request), T3D_E(t3d_pack_weights_batched), T3D_E(t3d_pwconv_pack_frag), T3D_E(t3d_adamw_step), T3D_E(t3d_set_grad_watch),
     T3D_E(t3d_sgd_step), T3D_E(t3d_rmsprop_step), T3D_E(t3d_adadelta_step),

@@ -63,7 +63,6 @@ SIGNATURES = {
     't3d_pwconv_fwd': [_I, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     't3d_pwconv_dgrad': [_I, _P, _P, _BP, _P, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     't3d_pack_weight': [_I, _P, _P, _I, _I, _I, _P],
-    't3d_sum_replicas_batched': [_P, _I, _I, _P],
     't3d_set_dw_slots': [_I, _P],
     't3d_set_exact_pool': [_I],
     't3d_set_launch_events': [_P, _P],
@@ -120,7 +119,6 @@ SIGNATURES = {
     't3d_bn_apply': [_I, _P, _PP, _P, _P, _I, _I, _P],
     't3d_bn_act_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _P],
     't3d_gap_fwd': [_I, _P, _PP, _P, _I, _I, _I, _P],
-    't3d_gap_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _I, _P],
     't3d_pool_fwd': [_I, _P, _PP, _I, _P, _P, _I, _I, _I, _P],
     't3d_pool_bwd': [_I, _P, _P, _PP, _I, _P, _P, _P, _I, _I, _I, _P],
     't3d_head_fwd': [_P, _PP, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
@@ -128,8 +126,6 @@ SIGNATURES = {
     't3d_head_fwd_all': [_P, _PP, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     't3d_head_bwd': [_P, _PP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     't3d_head_bwd_weights': [_P, _PP] + [_P] * 8 + [_I, _I, _I, _P],
-    't3d_se_fwd': [_P] * 11 + [_I, _I, _I, _I, _P],
-    't3d_se_bwd': [_P] * 18 + [_I, _I, _I, _I, _P],
     't3d_se_fwd_fused': [_P] * 11 + [_I] * 4 + [_P],
     't3d_se_bwd_data': [_P] * 13 + [_I] * 4 + [_P],
     't3d_se_bwd_weights': [_P] * 8 + [_I] * 3 + [_P],

@@ -21,6 +21,7 @@ Data layout in HBM
     tensors are views into it.
 There is no fallback: every op goes through libt3d_hip.so or raises.
 """
+import contextlib
 import math
 import os
 
@@ -32,15 +33,14 @@ from .arch import Arch
 BN_EPS, BN_MOM = 1e-5, 0.1      # PyTorch defaults the reference relies on
 NREP = 16                       # reduction replicas (include/t3d.h: t3d_set_reduction_replicas)
 FUSED_EVAL_MIN_B = int(os.environ.get('T3D_FUSED_EVAL_MIN_B', '96'))
-DW_SLOTS = int(os.environ.get('T3D_DW_SLOTS', '512'))   # depthwise weight-gradient slots per layer (>= the workgroups of a t3d_dwconv_bwd launch)
+DW_SLOTS = 512                  # depthwise weight-gradient slots per layer (>= the workgroups of a t3d_dwconv_bwd launch)
 WORKSPACE_BYTES = 64 << 20      # partial weight-gradient tiles (include/t3d.h: t3d_set_workspace)
 MAIN_WORKSPACE_BYTES = 16 << 20
 # y-free expand-layer backward (csrc/pwconv_yfree.hip): minimum M*N elements of the expanded tensor; 0 disables
 YFREE_MIN_ELEMS = int(os.environ.get('T3D_YFREE_MIN', 8 << 20))
-YFREE_MAX_K = int(os.environ.get('T3D_YFREE_MAX_K', 112))     # widest narrow side the y-free backward is used for (the K x K Gram terms); round 6: 96 -> 112 takes MobileNetV3-large's two 112 -> 672 expansions at 14x14 (7.59-7.65 -> 7.43 ms per step; 160, the 7x7 stage: 7.53)
+YFREE_MAX_K = 112               # widest narrow side the y-free backward is used for (the K x K Gram terms); round 6: 96 -> 112 takes MobileNetV3-large's two 112 -> 672 expansions at 14x14 (7.59-7.65 -> 7.43 ms per step; 160, the 7x7 stage: 7.53)
 HOOK_MIN = 1 << 20              # gradient-exchange granularity (elements): parallel.GradSync's bucket size
 SE_AFTER_FUSED = None            # gate-after backward: None = choose by shape (Net._se_after_fused)
-HOOK_ON_SIDE = True              # (round 3: the gradient exchange is issued from the second stream; the other order stalled the main one)
 
 
 def _se_after_fused_by_shape(dt, B, HW, C, R):
@@ -142,6 +142,17 @@ class Net:
         self._bufs = {}
         self._packed_dirty = True
         self._packed_version = -1
+        # device-resident descriptor tables, built by the first pass that needs them (each Net its own, `share` or not)
+        self._pack_desc = self._se_pack_desc = None            # _pack: 1x1 weights, squeeze-excite FCs (False: none)
+        self._evdesc = None                                    # _eval_affines
+        self._dwarena = self._zero_rows = None                 # _dw_arena_init, the backward's fixed clear rows
+        # batched clears (_buf / _zero_group / _zero): buffers registered per pass, what the cached descriptors cover
+        self._zgroups = {'fwd': {}, 'bwd': {}}
+        self._zcovered = {'fwd': frozenset(), 'bwd': frozenset()}
+        self._zgdesc, self._zdescs = {}, {}
+        self._want_taps = None        # forward_taps: the blocks whose finished outputs the pass keeps
+        self._dropout_calls = 0       # counter word of the dropout mask's generator
+        self.seed_rank = 0            # set by a data-parallel wrapper: independent dropout masks per rank
         self.saved = None
         self.generation = 0           # id of the latest train-mode forward (whose activations `saved` holds)
         # called as grad_hook(lo) once every gradient at flat offsets >= lo is final (backward runs from the
@@ -156,7 +167,7 @@ class Net:
         self.persistent_outputs = False
         # uint8 input path (include/t3d.h: t3d_stem_fwd, fmt 1): normalisation of configs/default_config.py:9-10
         self.set_input_normalization([0.5931, 0.4690, 0.4229], [0.2471, 0.2214, 0.2157])
-        self._fused_eval = not os.environ.get('T3D_NO_FUSED_EVAL')   # 14x14 / 7x7 blocks as one launch in inference mode
+        self._fused_eval = True       # 14x14 / 7x7 blocks as one launch in inference mode (tests turn it off to compare)
 
     def set_input_normalization(self, mean, std):
         """Per-channel mean / std applied to uint8 crops inside the stem kernel ((u/255 - mean) / std)."""
@@ -236,9 +247,6 @@ class Net:
             # addresses), few for the wide ones (whoever finalizes reads nrep x 2C doubles)
             b.nrep = _nrep_for(b.C)
         self._cur_nrep = None
-        # T3D_NO_LAZY_BN=1: every BatchNorm finalize as a launch of its own (the round-2 behaviour)
-        self._lazy = not os.environ.get('T3D_NO_LAZY_BN')
-        self._zfuse = True              # block outputs materialised by the consuming 1x1 conv (t3d_pwconv_fwd_mat)
         if sh is None:
             self.reset_parameters()
 
@@ -316,12 +324,10 @@ class Net:
             t = torch.empty(shape, device=self.device, dtype=dtype)
             self._bufs[key] = t
         if zgroup is not None:
-            zg = self.__dict__.setdefault('_zgroups', {'fwd': {}, 'bwd': {}})
-            cov = self.__dict__.setdefault('_zcovered', {'fwd': frozenset(), 'bwd': frozenset()})
             nb = t.numel() * t.element_size()
-            if (t.data_ptr(), nb) not in cov[zgroup]:
+            if (t.data_ptr(), nb) not in self._zcovered[zgroup]:
                 if nb % 16 == 0:
-                    zg[zgroup][(t.data_ptr(), nb)] = t          # on the list from the next pass on
+                    self._zgroups[zgroup][(t.data_ptr(), nb)] = t          # on the list from the next pass on
                 self._zero(t)
         elif zero:
             self._zero(t)
@@ -329,10 +335,8 @@ class Net:
 
     def _zero_group(self, group, extra_rows=()):
         """One t3d_zero_batched over `extra_rows` + every buffer registered for `group`; rebuilt when the list grew."""
-        zg = self.__dict__.setdefault('_zgroups', {'fwd': {}, 'bwd': {}})
-        cov = self.__dict__.setdefault('_zcovered', {'fwd': frozenset(), 'bwd': frozenset()})
-        desc = self.__dict__.setdefault('_zgdesc', {})
-        keys = frozenset(zg[group])
+        cov, desc = self._zcovered, self._zgdesc
+        keys = frozenset(self._zgroups[group])
         dk = (group, len(extra_rows))                 # (train / eval forwards differ in their fixed rows)
         if keys != cov[group]:
             for k in [k for k in desc if k[0] == group]:
@@ -353,7 +357,7 @@ class Net:
         kept per buffer): no framework launch inside the step, and a step plan being recorded sees the clear."""
         nb = t.numel() * t.element_size()
         if t.is_cuda and nb % 16 == 0 and t.is_contiguous():
-            zd = self.__dict__.setdefault('_zdescs', {})
+            zd = self._zdescs
             d = zd.get((t.data_ptr(), nb))
             if d is None:
                 d = zd[(t.data_ptr(), nb)] = torch.tensor([[t.data_ptr(), nb]], dtype=torch.int64, device=self.device)
@@ -373,7 +377,7 @@ class Net:
         if not self._packed_dirty and self._packed_version == self.flat._version:
             return
         st = N.stream()
-        if getattr(self, '_pack_desc', None) is None:
+        if self._pack_desc is None:
             # one descriptor table for every 1x1 weight: a single launch re-packs them all each step
             self.w, self.wt, rows = {}, {}, []
             # fragment-order copies (include/t3d.h: T3D_W_FRAG; the streaming kernel stages them with a linear copy, the
@@ -404,7 +408,7 @@ class Net:
             self._pack_desc = torch.tensor(rows, dtype=torch.int64, device=self.device)
         N.call('t3d_pack_weights_batched', self.dt, N.ptr(self._pack_desc), self._pack_desc.shape[0], st)
         # squeeze-excite FCs (nn.Linear, fp32): transposed copies for the one-launch forward (t3d_se_fwd_fused)
-        if getattr(self, '_se_pack_desc', None) is None:
+        if self._se_pack_desc is None:
             rows = []
             for k, (s, kind) in self.shapes.items():
                 if kind == 'param' and k in self._se_weights():
@@ -475,28 +479,24 @@ class Net:
     # that reads the coefficients either derives them in its own prologue (`_c(..., fwd=bn)` / `bwd=bn`: a request to the
     # entry points that implement it -- they fall back to a finalize launch of their own on paths without the prologue)
     # or is preceded by the standalone finalize (`_settle_f` / `_settle_b`: every other reader).
-    # (the depthwise kernels too -- T3D_LAZY_DW=0 | fwd | bwd | 1 --: every one of their 500-700 persistent workgroups then starts
-    # with the ~3-us round trip to the sums, but the 5-us finalize launch and the ~6-us dispatch gap behind it go: 7.90 -> 7.83
-    # ms per step on one box, 8.00 -> 7.97 on another (round 3b, forward half); with the atomics-free flush of round 3c the
-    # backward half costs nothing either (7.64 ms both ways, 18 launches fewer), so both are on)
-    _LAZY_DW = '1'
+    # (the depthwise kernels too: every one of their 500-700 persistent workgroups then starts with the ~3-us round trip to the
+    # sums, but the 5-us finalize launch and the ~6-us dispatch gap behind it go: 7.90 -> 7.83 ms per step in the forward half.
+    # With the atomics-free slot flush the backward half costs nothing either: 7.64 ms both ways, 18 launches fewer.)
     DERIVING = frozenset(('t3d_pwconv_fwd', 't3d_pwconv_fwd_mat', 't3d_bn_apply', 't3d_pool_fwd', 't3d_pwconv_dgrad', 't3d_pwconv_yfree_prep',
-                          't3d_pwconv_bwd_yfree_w', 't3d_se_bwd_affine')
-                         + (('t3d_dwconv_fwd',) if _LAZY_DW in ('1', 'fwd') else ())
-                         + (('t3d_dwconv_bwd',) if _LAZY_DW in ('1', 'bwd') else ()))
+                          't3d_pwconv_bwd_yfree_w', 't3d_se_bwd_affine', 't3d_dwconv_fwd', 't3d_dwconv_bwd'))
 
     def _c(self, entry, *args, fwd=None, bwd=None, **kw):
         """N.call of a coefficient-reading entry point: fwd / bwd = the BatchNorm whose forward / backward coefficients
         the launch reads first."""
         req = False
         if fwd is not None and fwd.pend[0]:
-            if self._lazy and entry in self.DERIVING:
+            if entry in self.DERIVING:
                 N.call('t3d_fold_request', N.ptr(self._fold_desc(fwd, 0, fwd.count)), N.ptr(fwd.scale))
                 fwd.pend[0], req = False, True
             else:
                 self._settle_f(fwd)
         if bwd is not None and bwd.pend[1]:
-            if self._lazy and entry in self.DERIVING and not req:
+            if entry in self.DERIVING and not req:
                 N.call('t3d_fold_request', N.ptr(self._fold_desc(bwd, 1, bwd.count)), N.ptr(bwd.alpha))
                 bwd.pend[1], req = False, True
             else:
@@ -544,7 +544,7 @@ class Net:
         return self._pro(bn, act)
 
     def _eval_affines(self):
-        if getattr(self, '_evdesc', None) is None:
+        if self._evdesc is None:
             rows = [[N.ptr(b.gamma), N.ptr(b.beta), N.ptr(b.rm), N.ptr(b.rv), N.ptr(b.scale), N.ptr(b.shift), b.C]
                     for b in self.bns.values()]
             self._evdesc = torch.tensor(rows, dtype=torch.int64, device=self.device)
@@ -590,17 +590,34 @@ class Net:
         else:
             N.call('t3d_set_main_workspace', None, 0)
 
-    def forward(self, imgs, cats, train=False, dropout_mask=None, all_heads=False):
+    @contextlib.contextmanager
+    def _pass(self, main_scratch=False, workspace=False):
+        """The library's process-wide state for the duration of one pass: the reduction replicas always, the main stream's
+        split-contraction scratch and the weight-gradient workspace where the pass has such products; left at the library's
+        defaults afterwards -- exact pool (the last squeeze-excite block leaves it on) and, after a backward, the depthwise
+        slots included.  The calls are part of a recorded step plan, so their order is fixed."""
         self._cur_nrep = None
         self._replicas(NREP)
-        self._main_scratch(True)
+        if workspace:
+            N.call('t3d_set_workspace', N.ptr(self._buf('workspace', (WORKSPACE_BYTES,), torch.uint8)), WORKSPACE_BYTES)
+        if main_scratch:
+            self._main_scratch(True)
         try:
-            return self._forward(imgs, cats, train, dropout_mask, all_heads)
+            yield
         finally:
             N.call('t3d_set_reduction_replicas', 1, 0)
+            if workspace:
+                N.call('t3d_set_dw_slots', 0, None)
             self._pool_exact(False)
             self._cur_nrep = None
-            self._main_scratch(False)
+            if workspace:
+                N.call('t3d_set_workspace', None, 0)
+            if main_scratch:
+                self._main_scratch(False)
+
+    def forward(self, imgs, cats, train=False, dropout_mask=None, all_heads=False):
+        with self._pass(main_scratch=True):
+            return self._forward(imgs, cats, train, dropout_mask, all_heads)
 
     def _forward(self, imgs, cats, train=False, dropout_mask=None, all_heads=False):
         """imgs [B,3,H,W] fp32 NCHW (the reference's input contract), cats int64 [B] ->
@@ -665,9 +682,9 @@ class Net:
             mask = dropout_mask
             if mask is None:        # nn.Dropout(0.5): keep with p = .5, scale by 2 (model_builder.py:83)
                 mask = self._buf('dropout', (B, a.feat_c), torch.float32)
-                self._dropout_calls = getattr(self, '_dropout_calls', 0) + 1
+                self._dropout_calls += 1
                 # (one process per GPU: main.py seeds every rank alike -- the rank term keeps the ranks' masks independent)
-                seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * getattr(self, 'seed_rank', 0)) & ((1 << 64) - 1)
+                seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self.seed_rank) & ((1 << 64) - 1)
                 N.call('t3d_dropout_mask', N.ptr(mask), B * a.feat_c, seed, self._dropout_calls, 0.5, st, slots={3: N.SLOT_DROPOUT})
             else:
                 mask = mask.to(self.device, torch.float32).contiguous()
@@ -687,30 +704,20 @@ class Net:
         """Inference pass over the backbone up to the last requested block: -> {k: (tensor [B*H*W, C] in the storage dtype,
         B, H, W, C)} with the finished (BatchNorm + skip applied) outputs of `features.k` -- the feature maps an SSD head
         taps (configs/detection/mnv2_ssd_300_2_heads.py:7-18: the 96- and 320-channel maps of mobilenetv2)."""
-        self._cur_nrep = None
-        self._replicas(NREP)
         self._want_taps = set(tap_blocks)
         try:
-            sv = self._features(imgs, False)
+            with self._pass():
+                sv = self._features(imgs, False)
         finally:
             self._want_taps = None
-            N.call('t3d_set_reduction_replicas', 1, 0)
-            self._pool_exact(False)          # (process-wide like the replicas: the last squeeze-excite block left it on)
-            self._cur_nrep = None
         return {k: (s.t, s.B, s.H, s.W, s.C) for k, s in sv['taps'].items()}
 
     def extract_features(self, imgs):
         """`MobileNetV3.extract_features` (mobilenetv3.py:199-203) as a caller sees it: the activated last feature map,
         fp32 NCHW [B, C, H/32, W/32].  Inference only (running BatchNorm statistics); the layout conversion from the
         engine's NHWC storage is a convenience for the API, not part of the hot path."""
-        self._cur_nrep = None
-        self._replicas(NREP)
-        try:
+        with self._pass():
             sv = self._features(imgs, False)
-        finally:
-            N.call('t3d_set_reduction_replicas', 1, 0)
-            self._pool_exact(False)          # (see forward_taps)
-            self._cur_nrep = None
         cur, a = sv['last_in'], self.arch
         M = sv['B'] * cur.H * cur.W
         z = torch.empty(M, a.last_c, device=self.device, dtype=self.dtype)
@@ -758,7 +765,7 @@ class Net:
         cur = _Src(y0, pro0, B, Ho, Wo, a.stem_c, raw=y0, bn=bn0, gpro=pro0)
         sv['col'], sv['stem'] = col, cur
 
-        taps = getattr(self, '_want_taps', None)
+        taps = self._want_taps
         for i, blk in enumerate(a.blocks):
             cur = self._block_fwd(i, blk, cur, sv)
             if taps and (i + 1) in taps:        # finished output of features.{i+1} (the detector's feature maps)
@@ -909,7 +916,7 @@ class Net:
             self._settle_f(bn2)          # the squeeze-excite kernels read bn2's affine first
         if se_after:
             # the gate sees the ACTIVATED tensor: one pooled pass over it, then the same two FCs (scale 1, shift 0, HW 1
-            # make t3d_se_fwd take the pooled mean as it is)
+            # make t3d_se_fwd_fused take the pooled mean as it is)
             C, R = blk.cexp, blk.se
             pooled = self._buf(f'se_pool:{i}', (B, C), torch.float32)
             N.call('t3d_gap_fwd', dt, N.ptr(y2), pro2, N.ptr(pooled), B, Ho * Wo, C, st)
@@ -951,7 +958,7 @@ class Net:
         out.zres, out.zbuf = (x.t if blk.res else None), z
         # (inference: only the fp32 engine keeps it pending -- its 1x1 kernel materialises on load, csrc/pwconv_f32_reg.hip; the
         # 16-bit inference engines read finished tensors in their fused block / expand + depthwise kernels)
-        if not ((self.training or self.dt == N.F32) and self._zfuse):
+        if not (self.training or self.dt == N.F32):
             self._resolve(out)
         rec.update(src=src, s2=s2, y3=y3, bn3=bn3, out=out, names=(dwn, pwn), blk=blk, idx=i)
         sv['blocks'].append(rec)
@@ -971,7 +978,7 @@ class Net:
         # (only where the bf16 transposed kernel will take the request: on the fp32-storage path the entry point would serve
         # it with a PUBLISHING finalize launch on the side stream while the data gradient of the main stream publishes the
         # same values -- there the standalone finalize runs once, on the main stream, ahead of both)
-        req = ro is not None and ro.pend[1] and self._lazy and entry == 't3d_pwconv_wgrad' and self.dt == N.BF16
+        req = ro is not None and ro.pend[1] and entry == 't3d_pwconv_wgrad' and self.dt == N.BF16
         if ro is not None and ro.pend[1] and not req:
             self._settle_b(ro)
         if req:
@@ -1017,20 +1024,8 @@ class Net:
             self._side_busy = False
 
     def backward(self, dkp, dlogits=None):
-        ws = self._buf('workspace', (WORKSPACE_BYTES,), torch.uint8)
-        self._cur_nrep = None
-        self._replicas(NREP)
-        N.call('t3d_set_workspace', N.ptr(ws), WORKSPACE_BYTES)
-        self._main_scratch(True)
-        try:
+        with self._pass(main_scratch=True, workspace=True):
             return self._backward(dkp, dlogits)
-        finally:
-            N.call('t3d_set_reduction_replicas', 1, 0)
-            N.call('t3d_set_dw_slots', 0, None)
-            self._pool_exact(False)
-            self._cur_nrep = None
-            N.call('t3d_set_workspace', None, 0)
-            self._main_scratch(False)
 
     def _backward(self, dkp, dlogits=None):
         """Gradient of the last train-mode forward w.r.t. every parameter -> `gflat` (overwritten).
@@ -1038,11 +1033,11 @@ class Net:
         sv = self.saved
         assert sv is not None, 'backward() needs a preceding forward(train=True)'
         a, st, dt, B = self.arch, N.stream(), self.dt, sv['B']
-        if getattr(self, '_dwarena', None) is None:
+        if self._dwarena is None:
             self._dw_arena_init()
         # one launch clears every accumulate-into buffer of the backward: gradients, depthwise replicas, stem patch-row dW
         dw32 = self._buf('dstem32', (a.stem_c, 32), torch.float32)
-        if getattr(self, '_zero_rows', None) is None:
+        if self._zero_rows is None:
             rows = [[t.data_ptr(), t.numel() * t.element_size()] for t in (self.gflat, dw32) if t.numel()]
             # (of a depthwise layer's slots only the first NREP: what a launch without slot support adds into)
             rows += [[v.data_ptr(), NREP * self.p[k].numel() * 4] for k, v in self._dwviews.items()]
@@ -1208,7 +1203,7 @@ class Net:
             return
         if force or self._hook_hi - lo >= HOOK_MIN:
             self._flush_dw()
-            if self._side is not None and HOOK_ON_SIDE and not force:      # (the last bucket: nothing left to overlap)
+            if self._side is not None and not force:      # (the last bucket: nothing left to overlap)
                 # the exchange has to see the weight gradients of the SECOND stream and the sums / BatchNorm gradients of the
                 # main one: issue it with the second stream current, after that stream has been made to wait for the main
                 # one -- the collective's own stream then waits for both, and the main stream waits for nobody (joining the

@@ -175,7 +175,7 @@ class StepPlan:
         net = model.net
         g, p = opt.param_groups[0], model.flat
         step = opt.advance(p)
-        net._dropout_calls = getattr(net, '_dropout_calls', 0) + 1
+        net._dropout_calls += 1
         s = self.slots
         s[N.SLOT_IMGS], s[N.SLOT_GT], s[N.SLOT_CATS] = imgs.data_ptr(), gt_kp.data_ptr(), cats.data_ptr()
         s[N.SLOT_DROPOUT], s[N.SLOT_STEP], s[N.SLOT_LR] = net._dropout_calls, step, N.double_bits(g['lr'])

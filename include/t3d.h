@@ -126,10 +126,6 @@ int t3d_pwconv_dgrad(int dtype, const void* dz, const void* y, const t3d_bnbwd* 
                      const void* x_raw, const t3d_prologue* pro_in, const void* residual, void* dx,
                      double* stats, float* ps_stats, int M, int HW, int K, int N, void* stream);
 
-/* Sum of reduction replicas for several tensors in one launch (the depthwise weight gradients of every layer finished
- * since the last call): desc = n rows of int64 {src, dst, count}, src [nrep][count] fp32 -> dst [count] fp32 (overwritten). */
-int t3d_sum_replicas_batched(const long long* desc, int n, int nrep, void* stream);
-
 /* Weight packing: fp32 master weight [rows,cols] -> storage dtype, optionally transposed to
  * [cols,rows] (the dgrad GEMM reads the transposed copy). */
 int t3d_pack_weight(int dtype, const float* w, void* out, int rows, int cols, int transpose, void* stream);
@@ -419,15 +415,12 @@ int t3d_bn_act_bwd(int dtype, const void* dz, const void* y, const t3d_prologue*
 int t3d_gap_fwd(int dtype, const void* y, const t3d_prologue* pro, float* pooled, int B, int HW, int C,
                 void* stream);
 
-/* ... and its backward: dz[b][hw][c] = dpooled[b][c]/HW * act'(scale*y + shift) (dtype),
- * stats [2*C] fp64 += sum(dz), sum(dz*y). */
-int t3d_gap_bwd(int dtype, const float* dpooled, const void* y, const t3d_prologue* pro, void* dz, double* stats,
-                int B, int HW, int C, void* stream);
-
-/* The other pooling modes of ModelWrapper._glob_feature_vector (model_builder.py:96-110): 'max'
+/* Every pooling mode of ModelWrapper._glob_feature_vector (model_builder.py:96-110): 'avg' (as t3d_gap_fwd), 'max'
  * (F.adaptive_max_pool2d(x, 1)) and 'avg+max' (their sum).  argmax [B,C] int32 receives the (h*W + w) position of
  * each maximum -- the first one in scan order among equal values, which is where PyTorch's backward routes the
- * gradient -- and is what t3d_pool_bwd reads back (may be NULL for T3D_POOL_AVG). */
+ * gradient -- and is what t3d_pool_bwd reads back (may be NULL for T3D_POOL_AVG).
+ * Backward: dz [B,HW,C] (dtype) = the pooled gradient routed back (T3D_POOL_AVG: dpooled[b][c]/HW at every pixel)
+ * * act'(scale*y + shift); stats [2*C] fp64 += sum(dz), sum(dz*y). */
 enum { T3D_POOL_AVG = 0, T3D_POOL_MAX = 1, T3D_POOL_AVGMAX = 2 };
 int t3d_pool_fwd(int dtype, const void* y, const t3d_prologue* pro, int mode, float* pooled, int* argmax, int B,
                  int HW, int C, void* stream);
@@ -504,17 +497,33 @@ int t3d_iou3d(const float* pred_kp, const float* gt_kp, int B, int portrait, con
  * the 8 corners), as `box.Box(vertices)` takes them (metrics.py:79-81) -> iou [B] fp64. */
 int t3d_box_iou3d(const double* verts, int B, double* iou, double* total, void* stream);
 
-/* Squeeze-excite gate (SELayer, mobilenetv3.py:92-107) from the depthwise kernel's per-sample sums:
- *   m = scale*gap_sum/HW + shift (= mean_hw of the BatchNorm output), h = relu(W1 m + b1), q = W2 h + b2,
- *   s = h_sigmoid(q).  gap_sum, m, q, s [B,C]; h [B,R]; W1 [R,C]; W2 [C,R]; all fp32. */
-int t3d_se_fwd(const float* gap_sum, const float* scale, const float* shift, const float* w1, const float* b1,
-               const float* w2, const float* b2, float* m, float* h, float* q, float* s, int B, int C, int R, int HW,
-               void* stream);
+/* Squeeze-excite gate (SELayer, mobilenetv3.py:92-107) from the depthwise kernel's per-sample sums, all fp32, C, R <= 1024:
+ *   m = scale*gap_sum/HW + shift (= mean_hw of the BatchNorm output), h = relu(W1 m + b1), q = W2 h + b2, s = h_sigmoid(q).
+ * _fwd_fused (two launches, one per product): gap_sum [B,C] (float sums; int64 fixed point after t3d_set_exact_pool(1)),
+ *   scale, shift [C], b1 [R], b2 [C] -> m, q, s [B,C], h [B,R].  It takes TRANSPOSED copies of the FC weights, so that its
+ *   contractions read [input][output] like the backward's: w1t [C,R] = W1^T, w2t [R,C] = W2^T for the parameters W1 [R,C]
+ *   (fc.0.weight) and W2 [C,R] (fc.2.weight); the caller keeps them current, e.g. with t3d_pack_weights_batched(T3D_F32, ...).
+ * _bwd_data (two launches): ps_stats [B,C,2] = per-sample P1 = sum_hw(dv), P2 = sum_hw(dv*y) from t3d_pwconv_dgrad (dv:
+ *   gradient at the gated tensor, y: raw depthwise output); gap_sum, scale, shift as in the forward; w1 [R,C], w2 [C,R]: the
+ *   parameters THEMSELVES; h, q, s: what the forward left.  With ds = scale*P2 + shift*P1 it writes
+ *   dq [B,C] = h_sigmoid'(q) ds, dp [B,R] = relu'(h) (dq W2) and g [B,C] = (dp W1) / HW, the pooled path's per-pixel gradient
+ *   (du = s*dv + g), and accumulates the depthwise BatchNorm's backward sums stats [2*C] fp64 += sum(du), sum(du*y) -- stats
+ *   may be NULL, and is spread over the reduction replicas of t3d_set_reduction_replicas like the conv kernels' sums.
+ * _bwd_weights OVERWRITES the FC gradients dw1 [R,C], db1 [R], dw2 [C,R], db2 [C] from m, h and the dq, dp that _bwd_data
+ *   (or t3d_se_after_bwd) left -- leaves of the backward graph, issued on the weight-gradient stream. */
+int t3d_se_fwd_fused(const float* gap_sum, const float* scale, const float* shift, const float* w1t, const float* b1,
+                     const float* w2t, const float* b2, float* m, float* h, float* q, float* s, int B, int C, int R, int HW,
+                     void* stream);
+int t3d_se_bwd_data(const float* ps_stats, const float* gap_sum, const float* scale, const float* shift, const float* w1,
+                    const float* w2, const float* h, const float* q, const float* s, float* g, float* dq, float* dp,
+                    double* stats, int B, int C, int R, int HW, void* stream);
+int t3d_se_bwd_weights(const float* m, const float* h, const float* dq, const float* dp, float* dw1, float* db1, float* dw2,
+                       float* db2, int B, int C, int R, void* stream);
 
 /* Squeeze-excite applied AFTER the activation (the no-expand block layout, mobilenetv3.py:138-140: dw -> BN -> act ->
  * SE -> 1x1; MobileNetV3-small features.1): v = s*a, a = act(scale*y + shift).  Forward: t3d_gap_fwd gives mean_hw(a),
- * t3d_se_fwd (scale = 1, shift = 0, HW = 1) the gate.  Backward, with dv [B*HW,C] the gradient at the gated tensor:
- *   _sums : ps [B,C,2] = { sum_hw dv*a, 0 }   -> t3d_se_bwd with scale = 0, shift = 1 (so that ds = ps[..][0]) gives g
+ * t3d_se_fwd_fused (scale = 1, shift = 0, HW = 1) the gate.  Backward, with dv [B*HW,C] the gradient at the gated tensor:
+ *   _sums : ps [B,C,2] = { sum_hw dv*a, 0 }   -> t3d_se_bwd_data with scale = 0, shift = 1 (so that ds = ps[..][0]) gives g
  *   _apply: du = (s*dv + g) * act'(scale*y + shift) at the BatchNorm output, stats [2*C] fp64 += sum(du), sum(du*y). */
 int t3d_se_after_sums(int dtype, const void* dv, const void* y, const t3d_prologue* pro, float* ps, int B, int HW, int C,
                       void* stream);
@@ -532,31 +541,6 @@ int t3d_se_after_apply(int dtype, const void* dv, const void* y, const t3d_prolo
 int t3d_se_after_bwd(int dtype, const void* dv, const void* y, const t3d_prologue* pro, const float* w1, const float* w2,
                      const float* h, const float* q, const float* s, float* g, float* dq, float* dp, void* du,
                      double* stats, int B, int HW, int C, int R, void* stream);
-
-/* Backward of the gate.  ps_stats [B,C,2] = per-sample sum_hw(dv), sum_hw(dv*y) from t3d_pwconv_dgrad
- * (dv: gradient at the gated tensor, y: raw depthwise output).  Produces g [B,C] (the pooled path's
- * per-pixel gradient, so that du = s*dv + g), accumulates the depthwise BatchNorm's backward sums
- * stats [2*C] fp64 += sum(du), sum(du*y), and OVERWRITES the FC gradients dw1 [R,C], db1 [R], dw2 [C,R], db2 [C].
- * dq [B,C], dp [B,R]: scratch. */
-int t3d_se_bwd(const float* ps_stats, const float* gap_sum, const float* scale, const float* shift, const float* w1,
-               const float* w2, const float* m, const float* h, const float* q, const float* s, float* g, float* dq,
-               float* dp, double* stats, float* dw1, float* db1, float* dw2, float* db2, int B, int C, int R, int HW,
-               void* stream);
-
-/* The same gate with ONE launch per direction (a workgroup per 8 samples walks both FCs; csrc/se.hip): what the host side
- * uses.  _fwd_fused takes TRANSPOSED fp32 copies of the FC weights (w1t [C][R] = fc.0.weight^T, w2t [R][C] = fc.2.weight^T;
- * e.g. kept current by t3d_pack_weights_batched(T3D_F32, ...)) and otherwise t3d_se_fwd's arguments.  _bwd_data is
- * t3d_se_bwd without the weight gradients (dq, dp stay behind for them; stats may be NULL, and is spread over the
- * reduction replicas of t3d_set_reduction_replicas like the conv kernels' sums); _bwd_weights computes dw1, db1, dw2, db2 from
- * m, h, dq, dp -- leaves of the backward graph, issued on the weight-gradient stream. */
-int t3d_se_fwd_fused(const float* gap_sum, const float* scale, const float* shift, const float* w1t, const float* b1,
-                     const float* w2t, const float* b2, float* m, float* h, float* q, float* s, int B, int C, int R, int HW,
-                     void* stream);
-int t3d_se_bwd_data(const float* ps_stats, const float* gap_sum, const float* scale, const float* shift, const float* w1,
-                    const float* w2, const float* h, const float* q, const float* s, float* g, float* dq, float* dp,
-                    double* stats, int B, int C, int R, int HW, void* stream);
-int t3d_se_bwd_weights(const float* m, const float* h, const float* dq, const float* dp, float* dw1, float* db1, float* dw2,
-                       float* db2, int B, int C, int R, void* stream);
 
 /* t3d_bn_apply + t3d_pwconv_fwd in one launch: the 1x1 conv whose input is the previous block's OUTPUT, still in its raw
  * form (models/mobilenetv3.py:158-166: `x + conv(x)` feeding the next block's expansion).  The operand
@@ -811,7 +795,7 @@ int t3d_set_reduction_replicas(int nrep, long long stats_stride);
 int t3d_set_dw_slots(int capacity, int* used_out);
 
 /* Squeeze-excite pooled sums without order noise.  on != 0: every `pooled` / `gap_sum` argument of the NEXT t3d_dwconv_fwd,
- * t3d_se_fwd(_fused), t3d_se_bwd(_data) calls addresses int64 [B][C] in units of 2^-24 instead of float [B][C] (zero it
+ * t3d_se_fwd_fused, t3d_se_bwd_data calls addresses int64 [B][C] in units of 2^-24 instead of float [B][C] (zero it
  * before the depthwise launch, as before): the depthwise kernel's work items add integers, which is associative, so the
  * sums -- and the gate torch computes from `y.mean((2, 3))` at models/mobilenetv3.py:100-104 -- are bit-reproducible from
  * run to run.  on == 0 (default): fp32 atomics into float [B][C].  Process-wide setting. */
