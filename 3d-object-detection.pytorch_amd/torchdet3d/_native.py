@@ -95,6 +95,8 @@ SIGNATURES = {
     't3d_ssd_multibox_work_bytes': [_I, _I],
     't3d_ssd_multibox_loss': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _F, _P, _P, _L,
                               _P, _P, _P, _P, _P, _P],
+    't3d_ssd_head_bwd_work_bytes': [_I, _P, _P, _P],
+    't3d_ssd_head_bwd': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _P],
     't3d_track_state_bytes': [_I],
     't3d_track_lds_bytes': [_I, _I],
     't3d_track_step': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _I, _D, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P],

@@ -18,8 +18,13 @@ unpinned** (no source, no weights); the layers themselves are the product's own 
   data       the config's train / test pipelines :63-143 on whole frames: `builders.build_detection_loader(cfg)` ->
              `GpuDetectionLoader` (dataloaders/detection.py, gpu_detection_loader.py; one t3d_detect_augment_u8 launch per
              batch), which yields exactly the (imgs, gt_boxes, gt_labels, gt_counts) `loss` takes and the uint8 frames `detect`
-             takes.  The backward through the heads and the tapped backbone is NOT built: the detector cannot be trained
-             end to end yet.
+             takes.
+  training   piece (b1), the heads: `head_backward` runs the heads with train-mode BatchNorm over the FROZEN backbone
+             (inference mode, running statistics, nothing of it changes), the MultiBox loss, t3d_ssd_head_bwd (the 1x1 half
+             of every head in one call, on the loss's fp32 gradients), t3d_bn_bwd_finalize and t3d_dwconv_bwd; the parameter
+             gradients land in the flat buffer `hgrad` (same layout as the parameters' `hflat`), the gradients at the two
+             taps come out on request.  `trainer.DetectorHeadTrainer` steps `hflat` with the config's SGD :145-153.  What is
+             left is (b2), the backward through the tapped backbone: the detector cannot be trained end to end yet.
 """
 import ctypes
 import math
@@ -28,7 +33,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .engine import Net
+from .engine import DW_SLOTS, Net
 
 INPUT_SIZE = 300
 CLASSES = ('bike', 'book', 'bottle', 'camera', 'cereal_box', 'chair', 'cup', 'laptop', 'shoe')     # config :4
@@ -43,6 +48,8 @@ STDS = (0.1, 0.1, 0.2, 0.2)                                                     
 TAPS = (13, 17)                  # features.13 -> 96 channels @ stride 16, features.17 -> 320 channels @ stride 32
 TAP_CHANNELS = (96, 320)
 BN_EPS = 1e-5
+BN_MOMENTUM = 0.1
+BRANCHES = ('cls_convs', 'reg_convs')
 
 
 def make_anchors(input_size=INPUT_SIZE):
@@ -73,6 +80,23 @@ def head_param_shapes(num_classes=len(CLASSES)):
     return out
 
 
+def flat_head_layout(num_classes=len(CLASSES)):
+    """{learnable state-dict entry: (offset, reserved elements)} in the flat parameter / gradient buffers.  A 1x1 conv's weight
+    and bias reserve their rows padded to a multiple of 8 -- the matrix and bias the kernels read --; the pad stays zero
+    (zero parameter, zero gradient: SGD with weight decay leaves it there).  Every offset is a multiple of 4 elements."""
+    out, off = {}, 0
+    for k, shp in head_param_shapes(num_classes).items():
+        if 'running' in k:
+            continue
+        n = int(np.prod(shp))
+        if '.3.' in k:
+            n = (shp[0] + 7) // 8 * 8 * (n // shp[0])
+        n = (n + 3) // 4 * 4
+        out[k] = (off, n)
+        off += n
+    return out
+
+
 class SSD300:
     """`detect(frames_u8)` -> per image an [n, 6] array (x1, y1, x2, y2 normalised to [0, 1], score, label)."""
 
@@ -90,8 +114,15 @@ class SSD300:
         self.backbone.reset_parameters(seed=seed)
         self.anchors = torch.from_numpy(make_anchors()).to(self.device)
         g = torch.Generator().manual_seed(seed + 1)
-        self.p = {}
-        for k, shp in head_param_shapes(num_classes).items():
+        # the learnable head parameters are views on ONE flat fp32 buffer (what t3d_sgd_step steps), their gradients views on
+        # `hgrad` of the same layout; the running statistics are tensors of their own
+        shapes = head_param_shapes(num_classes)
+        self.hlayout = flat_head_layout(num_classes)
+        total = max(o + n for o, n in self.hlayout.values())
+        self.hflat = torch.zeros((total + 3) // 4 * 4, device=self.device)
+        self.hgrad = torch.zeros_like(self.hflat)
+        self.p, self.hg = {}, {}
+        for k, shp in shapes.items():
             if k.endswith('running_var') or k.endswith('.1.weight'):
                 v = torch.ones(shp)
             elif k.endswith('.0.weight') or k.endswith('.3.weight'):
@@ -99,8 +130,15 @@ class SSD300:
                 v = torch.randn(shp, generator=g) * math.sqrt(2.0 / fan)
             else:
                 v = torch.zeros(shp)
-            self.p[k] = v.to(self.device)
+            if k in self.hlayout:
+                o, n = self.hlayout[k][0], v.numel()
+                self.p[k] = self.hflat[o:o + n].view(shp)
+                self.hg[k] = self.hgrad[o:o + n].view(shp)
+                self.p[k].copy_(v)
+            else:
+                self.p[k] = v.to(self.device)
         self._packed = None
+        self._train = {}
         self._stds = (ctypes.c_float * 4)(*STDS)
         self._persist, self._hbufs, self._dev = False, {}, {}
         self._mbox = None
@@ -117,7 +155,14 @@ class SSD300:
         self.backbone.load_state_dict(bb)
         for k in self.p:
             self.p[k].copy_(torch.as_tensor(sd[k]).to(self.device).view(self.p[k].shape))
+        self.params_changed()
+
+    def params_changed(self):
+        """After any change of the head parameters or running statistics: the eval-mode path folds the new values on its next
+        call, the training path repacks its 1x1 weights."""
         self._packed = None
+        for s in self._train.values():
+            s['stale'] = True
 
     def _pack(self):
         """1x1 weights in the storage dtype, output channels padded to a multiple of 8 (zero rows); BatchNorm folded to the
@@ -181,14 +226,142 @@ class SSD300:
         gt_boxes [B,G,4] fp32 in input pixels, gt_labels [B,G] int32, gt_counts [B] int32 -> `MultiBoxLoss.from_heads`'
         dict (the validation loss of the loaded checkpoint; with `with_grads` the gradients with respect to the head
         outputs, which a backward through the heads would consume).  Nothing is synchronised."""
+        outs = self.head_outputs(imgs)
+        return self._multibox().from_heads(outs, gt_boxes, gt_labels, gt_counts, with_grads=with_grads,
+                                           nanchors=[len(WIDTHS[l]) for l in range(len(outs))])
+
+    def _multibox(self):
         if self._mbox is None:
             from ..losses.detection_losses import MultiBoxLoss
             t = self.TRAIN_CFG
             self._mbox = MultiBoxLoss(self.anchors, self.nc, t['pos_iou_thr'], t['neg_iou_thr'], t['min_pos_iou'],
                                       t['neg_pos_ratio'], t['smoothl1_beta'], STDS)
-        outs = self.head_outputs(imgs)
-        return self._mbox.from_heads(outs, gt_boxes, gt_labels, gt_counts, with_grads=with_grads,
-                                     nanchors=[len(WIDTHS[l]) for l in range(len(outs))])
+        return self._mbox
+
+    # ------------------------------------------------------------------ training-mode heads (piece b1)
+    def _train_state(self, B, dims):
+        """The persistent buffers of `head_backward` at batch size B (a recorded plan points into them): per head the raw
+        depthwise output, the head output, the gradient at the BatchNorm output, the tap gradient, the BatchNorm's sums and
+        coefficients, the depthwise weight-gradient slots; and the host arrays t3d_ssd_head_bwd takes."""
+        s = self._train.get(B)
+        if s is not None:
+            return s
+        dev, f32 = self.device, torch.float32
+        heads = []
+        for l, (H, W, C) in enumerate(dims):
+            M = B * H * W
+            for br in BRANCHES:
+                p = f'bbox_head.{br}.{l}'
+                n = self.p[p + '.3.bias'].shape[0]
+                npad = (n + 7) // 8 * 8
+                o, _ = self.hlayout[p + '.3.weight']
+                ob, _ = self.hlayout[p + '.3.bias']
+                h = dict(l=l, br=br, p=p, M=M, H=H, W=W, C=C, n=n, ns=npad,
+                         w32=self.hflat[o:o + npad * C].view(npad, C), bias=self.hflat[ob:ob + npad],
+                         w=torch.zeros(npad, C, device=dev, dtype=self.dtype),
+                         y=torch.empty(M, C, device=dev, dtype=self.dtype), o=torch.empty(M, npad, device=dev, dtype=self.dtype),
+                         g=torch.empty(M, C, device=dev, dtype=self.dtype), dx=torch.empty(M, C, device=dev, dtype=self.dtype),
+                         coef=torch.zeros(7, C, device=dev, dtype=f32),      # scale, shift, mean, invstd, alpha, beta, gammac
+                         slots=torch.zeros(DW_SLOTS, C * 9, device=dev, dtype=f32))
+                h['pro'] = N.prologue(h['coef'][0], h['coef'][1], None, 'relu', False)
+                h['bb'] = N.bnbwd(h['coef'][4], h['coef'][5], h['coef'][6], False)
+                heads.append(h)
+        nh = len(heads)
+        # forward sums | backward sums of every head: one zero fill
+        offs = np.cumsum([0] + [4 * h['C'] for h in heads])
+        sums = torch.zeros(int(offs[-1]), device=dev, dtype=torch.float64)
+        used = torch.zeros(nh, device=dev, dtype=torch.int32)
+        for i, h in enumerate(heads):
+            h['stats'], h['bstats'] = sums[offs[i]:offs[i] + 2 * h['C']], sums[offs[i] + 2 * h['C']:offs[i + 1]]
+            h['used'] = used[i:i + 1]
+        P, I = ctypes.c_void_p * nh, ctypes.c_int * nh
+        geo = [I(*[h[k] for h in heads]) for k in ('M', 'C', 'n', 'ns')]
+        nb = N.lib().t3d_ssd_head_bwd_work_bytes(nh, *[ctypes.addressof(a) for a in geo[:3]])
+        if nb < 0:
+            raise RuntimeError(f't3d_ssd_head_bwd_work_bytes failed with code {nb}')
+        s = dict(heads=heads, sums=sums, used=used, geo=geo, work=torch.empty(nb // 8 + 1, device=dev, dtype=torch.float64), nb=nb,
+                 zero=torch.tensor([[sums.data_ptr(), sums.numel() * 8]], dtype=torch.int64, device=dev),
+                 pack=torch.tensor([[h['w32'].data_ptr(), h['w'].data_ptr(), 0, h['ns'], h['C'], 0, 0] for h in heads],
+                                   dtype=torch.int64, device=dev),
+                 flush=torch.tensor([[h['slots'].data_ptr(), self.hg[h['p'] + '.0.weight'].data_ptr(), h['C'] * 9,
+                                      h['used'].data_ptr()] for h in heads], dtype=torch.int64, device=dev),
+                 # (the loss's gradient pointers are filled in per call: `from_heads` allocates them)
+                 ptrs={k: P(*[t.data_ptr() for t in ts]) for k, ts in dict(
+                     y=[h['y'] for h in heads], scale=[h['coef'][0] for h in heads], shift=[h['coef'][1] for h in heads],
+                     w=[h['w'] for h in heads], g=[h['g'] for h in heads], stats=[h['bstats'] for h in heads],
+                     dW=[self.hg[h['p'] + '.3.weight'] for h in heads], dbias=[self.hg[h['p'] + '.3.bias'] for h in heads]).items()},
+                 P=P, stale=True)
+        self._train[B] = s
+        return s
+
+    def repack_heads(self, B=None):
+        """The heads' 1x1 weights in the storage dtype from `hflat`, every head in one launch (after an optimizer step)."""
+        for s in ([self._train[B]] if B is not None else self._train.values()):
+            N.call('t3d_pack_weights_batched', self.dt, N.ptr(s['pack']), s['pack'].shape[0], N.stream())
+            s['stale'] = False
+
+    @torch.no_grad()
+    def head_backward(self, imgs, gt_boxes, gt_labels, gt_counts, tap_grads=False):
+        """One training forward + backward of the four heads over the FROZEN backbone (the taps come from `forward_taps`:
+        inference mode, nothing of `self.backbone` changes).  The head BatchNorms run in training mode (the config's
+        norm_eval=False): batch statistics of count B*H*W, momentum 0.1, the running estimates updated with the unbiased
+        variance.  -> the dict of `MultiBoxLoss.from_heads` plus `dtaps`: with `tap_grads` the gradient at each tap
+        [B*H*W, C] in the storage dtype, class and box branch summed (else None).  The parameter gradients are left in
+        `hgrad` (views: `hg`).  Nothing is synchronised and every launch goes through `N.call`."""
+        taps = self.backbone.forward_taps(imgs, TAPS)
+        B = int(imgs.shape[0])
+        s = self._train_state(B, [taps[k][2:5] for k in TAPS])
+        st, heads, rec = N.stream(), s['heads'], N.recorder
+        if rec is not None:
+            rec.keep.append(s)
+        if s['stale'] or rec is not None:
+            self.repack_heads(B)
+        N.call('t3d_set_reduction_replicas', 1, 0)
+        N.call('t3d_zero_batched', N.ptr(s['zero']), 1, st)
+        # ---- forward: depthwise conv + batch sums -> affine (running estimates move) -> ReLU + 1x1 conv with bias
+        for h in heads:
+            t, M, H, W, C, c = taps[TAPS[h['l']]][0], h['M'], h['H'], h['W'], h['C'], h['coef']
+            p = h['p']
+            N.call('t3d_dwconv_fwd', self.dt, N.ptr(t), None, N.ptr(self.p[p + '.0.weight']), N.ptr(h['y']), N.ptr(h['stats']),
+                   None, B, H, W, C, 3, 1, st)
+            N.call('t3d_bn_finalize', N.ptr(h['stats']), C, float(M), N.ptr(self.p[p + '.1.weight']), N.ptr(self.p[p + '.1.bias']),
+                   N.ptr(self.p[p + '.1.running_mean']), N.ptr(self.p[p + '.1.running_var']), None, BN_MOMENTUM, BN_EPS,
+                   N.ptr(c[0]), N.ptr(c[1]), N.ptr(c[2]), N.ptr(c[3]), st)
+            N.call('t3d_pwconv_fwd', self.dt, N.ptr(h['y']), h['pro'], N.ptr(h['w']), N.ptr(h['bias']), N.ptr(h['o']), None,
+                   M, H * W, C, h['ns'], st)
+        self._packed = None           # (the running statistics moved: the eval path folds them again)
+        outs = [(heads[2 * l]['o'], heads[2 * l + 1]['o'], heads[2 * l]['H'] * heads[2 * l]['W']) for l in range(len(TAPS))]
+        r = self._multibox().from_heads(outs, gt_boxes, gt_labels, gt_counts, with_grads=True,
+                                        nanchors=[len(WIDTHS[l]) for l in range(len(TAPS))])
+        # ---- backward of the 1x1 half, every head in one call, on the loss's fp32 gradients
+        dout = s['P'](*[r['grads'][h['l']][BRANCHES.index(h['br'])].data_ptr() for h in heads])
+        if rec is not None:
+            rec.keep += [dout, r]
+        a = lambda x: ctypes.addressof(x)
+        pt = s['ptrs']
+        N.call('t3d_ssd_head_bwd', self.dt, len(heads), a(dout), a(pt['y']), a(pt['scale']), a(pt['shift']), a(pt['w']),
+               *[a(x) for x in s['geo']], N.ACT['relu'], a(pt['g']), a(pt['stats']), a(pt['dW']), a(pt['dbias']),
+               N.ptr(s['work']), s['nb'], st)
+        s['dout'] = dout              # (alive until the next call: the entry point reads the array before it returns)
+        # ---- BatchNorm backward -> dgamma, dbeta and the affine the depthwise backward applies; depthwise backward
+        dtaps = []
+        for i, h in enumerate(heads):
+            t, M, H, W, C, c = taps[TAPS[h['l']]][0], h['M'], h['H'], h['W'], h['C'], h['coef']
+            p = h['p']
+            N.call('t3d_bn_bwd_finalize', N.ptr(h['bstats']), C, float(M), N.ptr(self.p[p + '.1.weight']), N.ptr(c[2]), N.ptr(c[3]),
+                   N.ptr(c[4]), N.ptr(c[5]), N.ptr(c[6]), N.ptr(self.hg[p + '.1.weight']), N.ptr(self.hg[p + '.1.bias']), st)
+            N.call('t3d_set_dw_slots', DW_SLOTS, N.ptr(h['used']))
+            # (the entry point needs a dx buffer either way; the class branch's result is the box branch's `residual`)
+            res = heads[i - 1]['dx'] if (tap_grads and h['br'] == BRANCHES[1]) else None
+            N.call('t3d_dwconv_bwd', self.dt, N.ptr(h['g']), N.ptr(h['y']), h['bb'], N.ptr(self.p[p + '.0.weight']), N.ptr(t),
+                   None, N.ptr(res), N.ptr(h['dx']), None, N.ptr(h['slots']), B, H, W, C, 3, 1, st)
+            if tap_grads and h['br'] == BRANCHES[1]:
+                dtaps.append(h['dx'])
+        N.call('t3d_set_dw_slots', 0, None)
+        N.call('t3d_sum_slots_batched', N.ptr(s['flush']), len(heads), st)
+        r = dict(r)
+        r['dtaps'] = dtaps if tap_grads else None
+        return r
 
     @torch.no_grad()
     def detect_device(self, imgs):

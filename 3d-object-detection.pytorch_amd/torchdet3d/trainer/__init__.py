@@ -1,1 +1,2 @@
+from .detection import DetectorHeadTrainer
 from .train import Trainer

@@ -601,6 +601,33 @@ int t3d_ssd_multibox_loss(int dtype, int nlevels, const void* const* cls, const 
                           const float* stds, void* work, long long work_bytes, double* scalars, int* num_pos, int* assigned,
                           void* const* dcls, void* const* dreg, void* stream);
 
+/* Backward of the SSD heads' second half, ReLU(BatchNorm(y)) -> 1x1 conv + bias (csrc/ssd_head_bwd.hip): what training the
+ * SSDHead of configs/detection/mnv2_ssd_300_2_heads.py:15-37 under its optimizer / lr_config :145-153 needs between the
+ * MultiBox loss above and the depthwise layers, for EVERY head in one call of two launches (the pass, the ordered finish).
+ * Per head i (all arrays are HOST arrays of length nheads, device pointers in the pointer arrays):
+ *   dout  [M][ns] fp32: the loss's gradient at the head's output as t3d_ssd_multibox_loss wrote it (pad columns n..ns-1 are 0
+ *         by that contract; they are read and multiplied by zero, so they must be finite); never rounded to the storage dtype;
+ *   y     [M][C] (dtype): the raw depthwise output; scale, shift [C] fp32 and `act` (T3D_ACT_RELU, or T3D_ACT_NONE): the
+ *         prologue the forward 1x1 conv applied on load;  w [ns][C] (dtype): the matrix that conv multiplied by (rows past n
+ *         are not read);
+ *   g     [M][C] (dtype) = (dout . W) where fmaf(y, scale, shift) > 0 -- the forward's own comparison --, else 0: the gradient
+ *         at the BatchNorm output; the dot product runs in fp64, g is rounded once on store;
+ *   stats [2C] fp64 += sum(g), sum(g*y) of the unrounded g (what t3d_bn_bwd_finalize reads; the caller zeroes it);
+ *   dW    [n][C] fp32 = dout^T relu(fmaf(y, scale, shift)), OVERWRITTEN;  dbias [n] fp32 = column sums of dout, OVERWRITTEN.
+ * Sums over M: fp32 inside a workgroup's 128 rows (dW) or fp64 (the others), fp64 across workgroups, in a fixed order -- no
+ * floating-point atomics, two runs are bit-identical.
+ *   work: t3d_ssd_head_bwd_work_bytes(nheads, M, C, n) bytes of device scratch, 16-byte aligned (the query RETURNS the byte
+ *   count, or a negative T3D_ERR_*).
+ * T3D_ERR_UNSUPPORTED: C % 8 != 0, C > 1024, ns > 64, ns % 8 != 0, more than 8 heads, T3D_F16, another activation.
+ * T3D_ERR_ARG: n < 1, n > ns, M < 0, an unknown dtype, NULL or misaligned pointers (dout: 16 bytes), work_bytes too small.
+ * Every check precedes the first launch.  nheads == 0, or M == 0 for every head, launches nothing and returns T3D_OK; a head
+ * with M == 0 beside others gets dW = dbias = 0. */
+int t3d_ssd_head_bwd_work_bytes(int nheads, const int* M, const int* C, const int* n);
+int t3d_ssd_head_bwd(int dtype, int nheads, const void* const* dout, const void* const* y, const void* const* scale,
+                     const void* const* shift, const void* const* w, const int* M, const int* C, const int* n, const int* ns,
+                     int act, void* const* g, void* const* stats, void* const* dW, void* const* dbias, void* work,
+                     long long work_bytes, void* stream);
+
 /* The demo's third stage: IOUTracker.process + get_tracked_objects of torchdet3d/utils/tracking_tools.py:127-290 (Track:
  * :9-124; call site scripts/demo.py:56-78), one frame of S independent streams (cameras) per launch, one workgroup per
  * stream; the whole tracker state lives in device memory and nothing is read back.  Per stream, in the reference's order:
