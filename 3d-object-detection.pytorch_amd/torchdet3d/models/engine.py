@@ -151,6 +151,8 @@ class Net:
         self._zcovered = {'fwd': frozenset(), 'bwd': frozenset()}
         self._zgdesc, self._zdescs = {}, {}
         self._want_taps = None        # forward_taps: the blocks whose finished outputs the pass keeps
+        self._stop_after = None       # forward_taps_train: the pass ends behind this block (no last conv, pool, heads)
+        self._tap_res = {}            # backward_taps: {index of a tap's consumer block: the gradient at the tap}
         self._dropout_calls = 0       # counter word of the dropout mask's generator
         self.seed_rank = 0            # set by a data-parallel wrapper: independent dropout masks per rank
         self.saved = None
@@ -712,6 +714,85 @@ class Net:
             self._want_taps = None
         return {k: (s.t, s.B, s.H, s.W, s.C) for k, s in sv['taps'].items()}
 
+    def _check_train_taps(self, taps):
+        a = self.arch
+        if a.kind != 'mobilenet' or not taps or min(taps) < 1 or max(taps) > len(a.blocks):
+            raise NotImplementedError(f'tapped training pass: taps {sorted(taps)} of {self.name}')
+        for k in sorted(taps)[:-1]:          # (the deepest tap has no consumer: its sums come from a seed launch)
+            blk = a.blocks[k]                # features.{k+1}, the tap's consumer
+            if blk.res or not blk.expand:
+                # the tap gradient enters as the `residual` of the consumer's expansion data gradient; a consumer with a skip
+                # connection already uses that argument for the gradient at its own output
+                why = 'has a skip connection' if blk.res else 'has no expansion'
+                raise NotImplementedError(f'tapped training pass: the tap at features.{k} feeds features.{k + 1}, which {why}')
+
+    def forward_taps_train(self, imgs, tap_blocks):
+        """`forward_taps` in TRAINING mode (the detector config's norm_eval=False, frozen_stages=-1): the stem and
+        features.1 .. max(tap_blocks) normalise with their batch statistics, move their running estimates and count the
+        batch.  The pass ends behind the deepest tap: conv.0 / conv.1, the pool and the regression heads do not run and
+        nothing of theirs changes.  Keeps what `backward_taps` needs.  -> the dict of `forward_taps`."""
+        taps = set(int(k) for k in tap_blocks)
+        self._check_train_taps(taps)
+        if self.dt == N.F16:
+            raise RuntimeError('fp16 storage is an inference-only mode (build the model with storage_dtype bf16 or f32 to train)')
+        self.saved = None
+        self._want_taps, self._stop_after = taps, max(taps)
+        try:
+            with self._pass():
+                sv = self._features(imgs, True)
+        finally:
+            self._want_taps = self._stop_after = None
+        assert not any(b.pend[0] for b in self.bns.values()), 'a BatchNorm finalize was never run'
+        self.generation += 1
+        sv['generation'] = self.generation
+        sv['tap_order'] = sorted(taps)
+        self.saved = sv
+        return {k: (s.t, s.B, s.H, s.W, s.C) for k, s in sv['taps'].items()}
+
+    def backward_taps(self, dtaps):
+        """Gradient of the last `forward_taps_train` with respect to the parameters of the stem and of features.* ->
+        `gflat` (overwritten; every other element exactly 0).  dtaps: {k: gradient [B*H*W, C] at tap k in the storage
+        dtype}, one per tap of that pass.  Consumes the saved state."""
+        sv = self.saved
+        assert sv is not None and 'tap_order' in sv, 'backward_taps() needs a preceding forward_taps_train()'
+        assert sorted(dtaps) == sv['tap_order'], 'one gradient per tap of the forward'
+        for k, d in dtaps.items():
+            s = sv['taps'][k]
+            assert d.is_cuda and d.dtype == self.dtype and d.is_contiguous() and tuple(d.shape) == (s.B * s.H * s.W, s.C)
+        with self._pass(workspace=True):
+            self._backward_taps(sv, dtaps)
+
+    def _backward_taps(self, sv, dtaps):
+        a, st = self.arch, N.stream()
+        dw32 = self._clear_backward()
+        order = sv['tap_order']
+        deep = order[-1]
+        assert len(sv['blocks']) == deep
+        # (depthwise layers behind the deepest tap never run: the slot sums start at this pass's last block)
+        self._dwpending, self._hook_hi = 0, self.gflat.numel()
+        self._dwflushed = self._dworder.index(sv['blocks'][-1]['names'][0])
+        # ---- the deepest tap has no consumer: a seed launch takes its projection BatchNorm's backward sums sum(dz),
+        # sum(dz * y3) on the way (t3d_bn_act_bwd through the identity)
+        s = sv['taps'][deep]
+        M = s.B * s.H * s.W
+        dz = self._buf('dz:tap', (M, s.C))
+        N.call('t3d_bn_act_bwd', self.dt, N.ptr(dtaps[deep]), N.ptr(s.raw), None, N.ptr(dz), self._bst(s.bn), M, s.C, st)
+        # ---- every other tap joins as the `residual` of its consumer's expansion data gradient (added before the producer's
+        # sums are taken, exactly as a skip connection's gradient is)
+        self._tap_res = {k: dtaps[k] for k in order[:-1]}
+        try:
+            for rec in reversed(sv['blocks']):
+                dz = self._block_bwd(rec, dz)
+                self._maybe_hook(self.offsets[a.keys.blocks[rec['idx']].first][0])
+        finally:
+            self._tap_res = {}
+        self._stem_wgrad(sv, dz, dw32)
+        self._flush_dw()
+        self._join_side()
+        self._maybe_hook(0, force=True)
+        assert not any(b.pend[1] for b in self.bns.values()), 'a BatchNorm backward finalize was never run'
+        self.saved = None
+
     def extract_features(self, imgs):
         """`MobileNetV3.extract_features` (mobilenetv3.py:199-203) as a caller sees it: the activated last feature map,
         fp32 NCHW [B, C, H/32, W/32].  Inference only (running BatchNorm statistics); the layout conversion from the
@@ -770,6 +851,8 @@ class Net:
             cur = self._block_fwd(i, blk, cur, sv)
             if taps and (i + 1) in taps:        # finished output of features.{i+1} (the detector's feature maps)
                 sv.setdefault('taps', {})[i + 1] = self._resolve(cur)
+            if self._stop_after == i + 1:
+                return sv
 
         # ---- last 1x1 conv (mobilenetv3.py:118-123,188) + global average pool (model_builder.py:96-110)
         bnl = self.bns[a.keys.last_bn]
@@ -1027,16 +1110,12 @@ class Net:
         with self._pass(main_scratch=True, workspace=True):
             return self._backward(dkp, dlogits)
 
-    def _backward(self, dkp, dlogits=None):
-        """Gradient of the last train-mode forward w.r.t. every parameter -> `gflat` (overwritten).
-        dkp [B,9,2] / dlogits [B,num_classes]: d loss / d outputs (fp32)."""
-        sv = self.saved
-        assert sv is not None, 'backward() needs a preceding forward(train=True)'
-        a, st, dt, B = self.arch, N.stream(), self.dt, sv['B']
+    def _clear_backward(self):
+        """One launch clears every accumulate-into buffer of a backward: gradients, depthwise replicas, the stem's patch-row
+        dW (returned)."""
         if self._dwarena is None:
             self._dw_arena_init()
-        # one launch clears every accumulate-into buffer of the backward: gradients, depthwise replicas, stem patch-row dW
-        dw32 = self._buf('dstem32', (a.stem_c, 32), torch.float32)
+        dw32 = self._buf('dstem32', (self.arch.stem_c, 32), torch.float32)
         if self._zero_rows is None:
             rows = [[t.data_ptr(), t.numel() * t.element_size()] for t in (self.gflat, dw32) if t.numel()]
             # (of a depthwise layer's slots only the first NREP: what a launch without slot support adds into)
@@ -1044,6 +1123,15 @@ class Net:
             assert all(r[1] % 16 == 0 for r in rows)
             self._zero_rows = rows
         self._zero_group('bwd', self._zero_rows)      # + the squeeze-excite per-sample sums (`zgroup='bwd'` buffers)
+        return dw32
+
+    def _backward(self, dkp, dlogits=None):
+        """Gradient of the last train-mode forward w.r.t. every parameter -> `gflat` (overwritten).
+        dkp [B,9,2] / dlogits [B,num_classes]: d loss / d outputs (fp32)."""
+        sv = self.saved
+        assert sv is not None and 'tap_order' not in sv, 'backward() needs a preceding forward(train=True)'
+        a, st, dt, B = self.arch, N.stream(), self.dt, sv['B']
+        dw32 = self._clear_backward()
         self._dwpending, self._dwflushed, self._hook_hi = 0, 0, self.gflat.numel()
         dkp = dkp.reshape(B, 18).to(torch.float32).contiguous()
         ncls = self.num_classes
@@ -1131,7 +1219,11 @@ class Net:
             dz = self._block_bwd(rec, dz)
             self._maybe_hook(self.offsets[a.keys.blocks[rec['idx']].first][0])
 
-        # ---- stem weight gradient
+        self._stem_wgrad(sv, dz, dw32)
+
+    def _stem_wgrad(self, sv, dz, dw32):
+        """The stem's weight gradient from dz, the gradient at its BatchNorm's output (the end of every backbone backward)."""
+        a, st, dt = self.arch, N.stream(), self.dt
         s0 = sv['stem']
         bn0 = s0.bn
         bb = self._bn_bwd(bn0)
@@ -1380,7 +1472,7 @@ class Net:
         B = x.B
         M2 = s2.B * s2.H * s2.W
         M1 = B * x.H * x.W
-        res = dz if blk.res else None
+        res = dz if blk.res else self._tap_res.get(i)       # (backward_taps: a tap's gradient joins at its consumer)
         if blk.expand:
             s1 = rec['s1']
             d1 = self._buf(f'dz1:{i}', (M1, blk.cexp))

@@ -23,8 +23,11 @@ unpinned** (no source, no weights); the layers themselves are the product's own 
              (inference mode, running statistics, nothing of it changes), the MultiBox loss, t3d_ssd_head_bwd (the 1x1 half
              of every head in one call, on the loss's fp32 gradients), t3d_bn_bwd_finalize and t3d_dwconv_bwd; the parameter
              gradients land in the flat buffer `hgrad` (same layout as the parameters' `hflat`), the gradients at the two
-             taps come out on request.  `trainer.DetectorHeadTrainer` steps `hflat` with the config's SGD :145-153.  What is
-             left is (b2), the backward through the tapped backbone: the detector cannot be trained end to end yet.
+             taps come out on request.  `trainer.DetectorHeadTrainer` steps `hflat` with the config's SGD :145-153.
+             Piece (b2), the backbone: `train_backward` runs the tapped backbone in training mode
+             (`Net.forward_taps_train`), the same head half, and sends the tap gradients through `Net.backward_taps` -- the
+             middle tap joins as the residual of features.14's expansion data gradient, the deepest one enters through a
+             t3d_bn_act_bwd seed launch; `trainer.DetectorTrainer` steps `hflat` and the backbone's trained prefix of `flat`.
 """
 import ctypes
 import math
@@ -308,8 +311,11 @@ class SSD300:
         variance.  -> the dict of `MultiBoxLoss.from_heads` plus `dtaps`: with `tap_grads` the gradient at each tap
         [B*H*W, C] in the storage dtype, class and box branch summed (else None).  The parameter gradients are left in
         `hgrad` (views: `hg`).  Nothing is synchronised and every launch goes through `N.call`."""
-        taps = self.backbone.forward_taps(imgs, TAPS)
-        B = int(imgs.shape[0])
+        return self._heads_fwd_bwd(self.backbone.forward_taps(imgs, TAPS), int(imgs.shape[0]), gt_boxes, gt_labels, gt_counts,
+                                   tap_grads)
+
+    def _heads_fwd_bwd(self, taps, B, gt_boxes, gt_labels, gt_counts, tap_grads):
+        """The head half of `head_backward` / `train_backward` on given taps (the dict of `Net.forward_taps`)."""
         s = self._train_state(B, [taps[k][2:5] for k in TAPS])
         st, heads, rec = N.stream(), s['heads'], N.recorder
         if rec is not None:
@@ -361,6 +367,22 @@ class SSD300:
         N.call('t3d_sum_slots_batched', N.ptr(s['flush']), len(heads), st)
         r = dict(r)
         r['dtaps'] = dtaps if tap_grads else None
+        return r
+
+    @torch.no_grad()
+    def train_backward(self, imgs, gt_boxes, gt_labels, gt_counts):
+        """One training forward + backward of the WHOLE detector (piece (b2); the config's norm_eval=False,
+        frozen_stages=-1): the tapped backbone in training mode (`Net.forward_taps_train`: batch statistics, running
+        estimates moved), the head half of `head_backward` on those taps, and the tap gradients sent back through
+        `Net.backward_taps`.  Head gradients land in `hgrad`, backbone gradients in `backbone.gflat` (zero outside the stem
+        and features.*).  -> the dict of `head_backward` with the tap gradients.  Nothing is synchronised and every launch
+        goes through `N.call`."""
+        bb = self.backbone
+        taps = bb.forward_taps_train(imgs, TAPS)
+        # (the engine's pass has settled every BatchNorm the taps were read through and left the library's process-wide state
+        # at its defaults, which is what the head half starts from; `backward_taps` sets its own again)
+        r = self._heads_fwd_bwd(taps, int(imgs.shape[0]), gt_boxes, gt_labels, gt_counts, True)
+        bb.backward_taps(dict(zip(TAPS, r['dtaps'])))
         return r
 
     @torch.no_grad()

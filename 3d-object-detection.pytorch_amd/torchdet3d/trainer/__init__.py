@@ -1,2 +1,2 @@
-from .detection import DetectorHeadTrainer
+from .detection import DetectorHeadTrainer, DetectorTrainer
 from .train import Trainer
