@@ -82,7 +82,7 @@ const Entry kEntries[] = {
     T3D_E(t3d_loss_fwd_bwd), T3D_E(t3d_metrics_per_sample), T3D_E(t3d_iou3d), T3D_E(t3d_box_iou3d), T3D_E(t3d_ssd_decode_nms),
     T3D_E(t3d_expdw_fwd), T3D_E(t3d_track_step), T3D_E(t3d_ssd_select_rects), T3D_E(t3d_head_select), T3D_E(t3d_track_kp_to_frame),
     T3D_E(t3d_objectron_pairs), T3D_E(t3d_objectron_hitmiss), T3D_E(t3d_draw_overlays_u8), T3D_E(t3d_ssd_multibox_loss),
-    T3D_E(t3d_ssd_head_bwd),
+    T3D_E(t3d_ssd_head_bwd), T3D_E(t3d_ssd_cap_per_image), T3D_E(t3d_coco_match),
 };
 #undef T3D_E
 constexpr int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));

@@ -107,6 +107,8 @@ SIGNATURES = {
     't3d_draw_glyphs': [_P, _I],
     't3d_objectron_pairs': [_P] * 7 + [_I, _I, _I, _D, _D, _P, _P, _P],
     't3d_objectron_hitmiss': [_P] * 8 + [_I] * 5 + [_P] * 6,
+    't3d_ssd_cap_per_image': [_P, _P, _I, _I, _I, _I, _P, _P],
+    't3d_coco_match': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I] + [_P] * 7,
     't3d_im2col': [_I, _P, _PP, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     't3d_im2col_nchw': [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     't3d_col2im_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

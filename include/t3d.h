@@ -766,6 +766,58 @@ int t3d_objectron_hitmiss(const double* metrics, const int* matched, const int* 
                           int F, int P, int G, int base, int capacity, int* valid, int* num_instances, int* hit, int* miss,
                           double* sums, void* stream);
 
+/* COCO bbox evaluation of the detector on the device (csrc/detection_eval.hip): the per-image half of the published
+ * pycocotools COCOeval with iouType = 'bbox', as mmdet 2.x's CocoDataset.evaluate(metric='bbox') drives it for
+ * configs/detection/mnv2_ssd_300_2_heads.py:56-60,130-143.  pycocotools is not installed where this project is built:
+ * DESIGN.md section 7 states the protocol, tests/coco_eval_ref.py restates it as loops, parity with the package is unpinned.
+ * Deviations: no crowd branch (annotation_converters/objectron_2_coco.py:170 writes iscrowd = 0 everywhere), NMS at input
+ * scale before the rescale where mmdet rescales first, no xywh round trip through JSON.
+ *
+ * t3d_ssd_cap_per_image: mmdet's test_cfg.max_per_img on the device, one workgroup per image.
+ *   out [B][num_classes][max_per_class][6] fp32 / counts [B][num_classes] int32 as t3d_ssd_decode_nms leaves them (counts
+ *   clamped to [0, max_per_class]; only column 4, the score, of the rows below a count is read; `out` is never written).
+ *   Of all valid rows of an image the first max_per_img survive in the order score descending (a nan last), then class
+ *   ascending, then row ascending -- numpy's stable argsort of -score over the classes' rows concatenated, which is what
+ *   SSD300.merge_classes does on the host.  counts_out [B][num_classes] int32 = the survivors of each class; with the rows of
+ *   a class in non-increasing score order (the decode kernel's greedy NMS emits them so) they are the class's first
+ *   counts_out rows.  counts_out may be `counts` itself.
+ *   T3D_ERR_ARG: NULL or misaligned pointers, B < 0, num_classes < 1, max_per_class < 1, max_per_img < 0.
+ *   T3D_ERR_UNSUPPORTED: num_classes * max_per_class > 4096 (an image's scores are ranked in LDS).  B == 0: T3D_OK, no launch.
+ *
+ * t3d_coco_match: COCOeval.evaluateImg for every (image, class) of a batch, one workgroup per cell, into rows
+ * base .. base + B - 1 of a record of R rows.
+ *   out / counts as above (counts already capped); gt_boxes [B][G][4] fp32 (x1, y1, x2, y2 in input pixels), gt_labels
+ *   [B][G] int32, gt_counts [B] int32 clamped to [0, G]: a slot below the count is used when its coordinates are finite,
+ *   x2 > x1, y2 > y1 and 0 <= label < num_classes, and skipped as if absent otherwise (the rule of t3d_ssd_multibox_loss);
+ *   both may be NULL when G == 0.  ori_shapes [B][2] int32 = (h, w) of the original frame, (in_w, in_h) the network input;
+ *   iou_thrs [10] fp64, area_rngs [4][2] fp64 (lo, hi), both computed by the HOST (numpy.linspace; never on the device).
+ *   Coordinates: fx = (double)w / (double)in_w, fy = (double)h / (double)in_h, X = (double)x * fx, Y = (double)y * fy,
+ *   area = (X2 - X1) * (Y2 - Y1); fp64 from there on, every operation rounded on its own.
+ *   Detections of a cell: its first min(counts, 100) rows, taken to be in non-increasing score order.
+ *   IoU(d, g): iw = min(dX2, gX2) - max(dX1, gX1), ih likewise; 0 when iw <= 0 or ih <= 0, else i = iw * ih,
+ *   i / (ad + ag - i).
+ *   Per area range a and threshold t: a ground truth is ignored when ag < lo[a] or ag > hi[a]; ground truths are walked
+ *   non-ignored first, then ignored, each group in slot order; per detection thr = min(T[t], 1 - 1e-10), m = none; a ground
+ *   truth already matched at (a, t) is skipped; the walk STOPS when m is set, m is not ignored and this one is; one with
+ *   iou < thr is skipped; otherwise thr = iou, m = this one (equality matches: among equal IoUs the later wins).  A matched
+ *   detection gets dtm = 1, dtig = ignored(m), and m is taken; an unmatched one dtig = (ad < lo[a] or ad > hi[a]).
+ *   Record row r = base + b, every slot written (nothing needs clearing):
+ *     rec_score [R][num_classes][100] fp32 (0 past the cell's detections);
+ *     rec_dtm / rec_dtig [R][num_classes][100] uint64, bit a * 10 + t (0 past the cell's detections);
+ *     rec_ndt [R][num_classes] int32; rec_ngt [R][num_classes][4] int32 = non-ignored ground truths per area range;
+ *     rec_valid [R] int32 = 1, or 0 for a frame with h <= 0 or w <= 0, whose row is then empty.
+ *   T3D_ERR_UNSUPPORTED: G > 64 (the IoU matrix of a cell lives in LDS; the loss kernel's bound).
+ *   T3D_ERR_ARG: NULL or misaligned pointers (8 bytes for the fp64 / uint64 ones), B, G, base or R < 0, base + B > R,
+ *   num_classes < 1, max_per_class < 1, in_w <= 0 or in_h <= 0.  B == 0 returns T3D_OK without a launch.  Every check
+ *   precedes the launch.  No atomics: each cell has one owner, two runs are bit-identical.  Both only enqueue on `stream`. */
+int t3d_ssd_cap_per_image(const float* out, const int* counts, int B, int num_classes, int max_per_class, int max_per_img,
+                          int* counts_out, void* stream);
+int t3d_coco_match(const float* out, const int* counts, int B, int num_classes, int max_per_class, const float* gt_boxes,
+                   const int* gt_labels, const int* gt_counts, int G, const int* ori_shapes, int in_w, int in_h,
+                   const double* iou_thrs, const double* area_rngs, int base, int R, float* rec_score,
+                   unsigned long long* rec_dtm, unsigned long long* rec_dtig, int* rec_ndt, int* rec_ngt, int* rec_valid,
+                   void* stream);
+
 /* ---- ResNet-50 backbone (BASELINE config 4; the reference has no ResNet -- standard torchvision architecture, parity
  * against oracle/resnet.py, unpinned).  Dense k x k convolutions run as patch gather + the pointwise GEMM entry points
  * (t3d_pwconv_fwd / _dgrad / _wgrad with K = Kp); everything below is an HBM-bound gather / elementwise kernel. ---- */
