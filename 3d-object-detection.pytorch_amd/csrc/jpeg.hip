@@ -1,0 +1,120 @@
+// Baseline JPEG frames decoded on the device from the host's MCU index: t3d_jpeg_index (host only, csrc/jpeg_index.h) and
+// t3d_jpeg_decode_u8.  include/t3d.h states the arithmetic (libjpeg's JDCT_ISLOW + fancy upsampling, all integer); the numpy
+// restatement tests/jpeg_ref.py and Pillow on libjpeg-turbo agree with it bit for bit.
+//
+// One call is two memsets (coefficients, status) and three kernels, whatever the batch:
+//   entropy   one lane per SEGMENT (seg_mcus consecutive MCUs), one wave per workgroup, the workgroups of grid row y share
+//             image y: its four Huffman tables are expanded into LDS once (a 9-bit first-level lookup + the canonical slow
+//             path), every lane then runs the serial decode of its own segment from the indexed bit position with a 64-bit
+//             window, four stream bytes per refill.  Lanes diverge (that is the nature of the format); what they share is the
+//             table in LDS.  Non-zero quantised coefficients go to zeroed int16 blocks in natural order.
+//   idct      one lane per 8x8 block: dequantise, the two islow passes in registers, one uint8 plane per component.
+//   colour    four consecutive pixels per lane: chroma upsampling (4:2:0) and YCbCr -> RGB, three dword stores where the image
+//             is dword aligned (a 1440 x 1920 frame is), bytes where it is not.
+// Memory safety is in the code, not in the stream: the reader clamps every index to the image's scan and feeds zeros behind
+// it, the block loop ends at coefficient 63, a lane stays inside its segment's blocks, and every per-image range is checked
+// against the buffers before anything of that image is touched (status 2).
+#include "common.h"
+#include "jpeg_decode.h"
+
+extern "C" int t3d_jpeg_index(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info, t3d_jpeg_seg* segs,
+                              long long seg_capacity) {
+  return t3d_jpeg_index_impl(data, bytes, seg_mcus, info, segs, seg_capacity);
+}
+
+namespace {
+
+namespace L = t3d_jpeg_lane;
+static_assert(sizeof(t3d_jpeg_info) == 864 && sizeof(t3d_jpeg_seg) == 16 && sizeof(t3d_jpeg_item) == 48, "include/t3d.h");
+
+#define JPEG_ARGS                                                                                                              \
+  const unsigned char *__restrict__ data, long long data_bytes, const t3d_jpeg_info *__restrict__ infos,                       \
+      const t3d_jpeg_seg *__restrict__ segs, long long total_segs, const t3d_jpeg_item *__restrict__ items, unsigned char *out, \
+      long long out_bytes, void *work, long long total_blocks
+#define JPEG_GEOM(img) L::geom(data, data_bytes, infos + (img), segs, total_segs, items[img], out, out_bytes, work, total_blocks)
+
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JPEG_ARGS, int* __restrict__ status) {
+  __shared__ t3d_jpeg_huff tab[4];                      // DC 0, DC 1, AC 0, AC 1
+  __shared__ int tab_ok[4];
+  const int img = blockIdx.y;
+  const t3d_jpeg_info* info = infos + img;
+  const L::Geom g = JPEG_GEOM(img);
+  if (!g.ok) {                                          // (uniform in the workgroup)
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[img] = 2;
+    return;
+  }
+  if (threadIdx.x < 4) {
+    const int t = threadIdx.x & 1;
+    tab_ok[threadIdx.x] = threadIdx.x < 2 ? t3d_jpeg_build_huff(info->dc_bits[t], info->dc_vals[t], 16, &tab[threadIdx.x])
+                                          : t3d_jpeg_build_huff(info->ac_bits[t], info->ac_vals[t], 256, &tab[threadIdx.x]);
+  }
+  __syncthreads();
+  int dci[3], aci[3];
+  bool tables = true;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    dci[c] = c < g.ncomp ? info->comp_dc[c] : 0;        // (0 or 1: L::geom checked them)
+    aci[c] = 2 + (c < g.ncomp ? info->comp_ac[c] : 0);
+    tables = tables && tab_ok[dci[c]] && tab_ok[aci[c]];
+  }
+  if (!tables) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[img] = 2;
+    return;
+  }
+  for (int s = blockIdx.x * 64 + threadIdx.x; s < g.nseg; s += gridDim.x * 64)
+    if (!L::decode_segment(g, tab, dci, aci, s)) status[img] = 1;
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(JPEG_ARGS) {
+  __shared__ int quant[3 * 64];
+  const int img = blockIdx.y;
+  const L::Geom g = JPEG_GEOM(img);
+  if (!g.ok) return;
+  if (threadIdx.x < 192) quant[threadIdx.x] = infos[img].quant[threadIdx.x >> 6][threadIdx.x & 63];
+  __syncthreads();
+  for (long long blk = blockIdx.x * 256ll + threadIdx.x; blk < g.nblocks; blk += gridDim.x * 256ll) L::idct_block(g, quant, blk);
+}
+
+__global__ __launch_bounds__(256) void jpeg_colour_kernel(JPEG_ARGS) {
+  const L::Geom g = JPEG_GEOM(blockIdx.y);
+  if (!g.ok) return;
+  const long long nrun = ((long long)g.h * g.w + 3) / 4;
+  const bool aligned = (reinterpret_cast<uintptr_t>(g.out) & 3) == 0;        // (uniform in the workgroup)
+  for (long long t = blockIdx.x * 256ll + threadIdx.x; t < nrun; t += gridDim.x * 256ll) L::colour_run(g, t, aligned);
+}
+
+}  // namespace
+
+extern "C" int t3d_jpeg_decode_work_bytes(long long total_blocks, long long* bytes) {
+  if (!bytes || total_blocks < 0 || total_blocks > (1ll << 40)) return T3D_ERR_ARG;
+  *bytes = total_blocks * 192;
+  return T3D_OK;
+}
+
+extern "C" int t3d_jpeg_decode_u8(const unsigned char* data, long long data_bytes, const t3d_jpeg_info* infos, const t3d_jpeg_seg* segs,
+                                  long long total_segs, const t3d_jpeg_item* items, unsigned char* out, long long out_bytes, void* work,
+                                  long long work_bytes, long long total_blocks, int* status, int B, int max_segs, int max_blocks,
+                                  void* stream) {
+  if (B < 0 || B > 65535) return T3D_ERR_ARG;
+  if (B == 0) return T3D_OK;
+  if (!data || !infos || !segs || !items || !out || !work || !status) return T3D_ERR_ARG;
+  if (data_bytes <= 0 || total_segs <= 0 || out_bytes <= 0 || total_blocks <= 0 || total_blocks > (1ll << 40)) return T3D_ERR_ARG;
+  if (max_segs < 1 || max_blocks < 1) return T3D_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < total_blocks * 192) return T3D_ERR_ARG;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(work, 0, (size_t)total_blocks * 128, st) != hipSuccess) return T3D_ERR_LAUNCH;
+  if (hipMemsetAsync(status, 0, sizeof(int) * (size_t)B, st) != hipSuccess) return T3D_ERR_LAUNCH;
+  const unsigned int gs = (unsigned int)min(max_segs / 64 + 1, 65535);
+  T3D_LAUNCH(jpeg_entropy_kernel, dim3(gs, B), dim3(64), 0, st, data, data_bytes, infos, segs, total_segs, items, out, out_bytes, work,
+             total_blocks, status);
+  T3D_CHECK_LAUNCH();
+  const unsigned int gb = (unsigned int)min(max_blocks / 256 + 1, 4096);
+  T3D_LAUNCH(jpeg_idct_kernel, dim3(gb, B), dim3(256), 0, st, data, data_bytes, infos, segs, total_segs, items, out, out_bytes, work,
+             total_blocks);
+  T3D_CHECK_LAUNCH();
+  const unsigned int gc = (unsigned int)min((max_blocks * 16ll + 255) / 256, 4096ll);      // a block is 64 samples = 16 runs of 4 pixels
+  T3D_LAUNCH(jpeg_colour_kernel, dim3(gc, B), dim3(256), 0, st, data, data_bytes, infos, segs, total_segs, items, out, out_bytes, work,
+             total_blocks);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}

@@ -1,0 +1,336 @@
+// What ONE LANE of the device JPEG decode does (csrc/jpeg.hip launches it; include/t3d.h states the arithmetic): the checked
+// per-image geometry, the bit reader, the decode of one segment, the inverse DCT of one block, one run of four output pixels.
+// Like csrc/jpeg_index.h it has no HIP include, so the very code the kernels run also compiles for the host, where
+// tools/jpeg_index_check.cpp walks it under the address and undefined-behaviour sanitizers.
+#pragma once
+#include "jpeg_index.h"
+
+#ifdef __HIPCC__
+#define T3D_JPEG_LANE __device__ __forceinline__
+#else
+#define T3D_JPEG_LANE inline
+#endif
+
+namespace t3d_jpeg_lane {
+
+template <class T> T3D_JPEG_LANE T lo(T a, T b) { return a < b ? a : b; }
+template <class T> T3D_JPEG_LANE T hi(T a, T b) { return a > b ? a : b; }
+T3D_JPEG_LANE int clamp255(int v) { return lo(hi(v, 0), 255); }
+struct alignas(16) Int4 { int x, y, z, w; };
+struct alignas(8) UInt2 { unsigned int x, y; };
+
+// What the kernels need of one image, or ok == false.  Every field is checked here, by every kernel, before it is used.
+struct Geom {
+  bool ok;
+  int h, w, ncomp, sampling, mcus_x, mcus_y, nmcu, seg_mcus, nseg, bpm;      // bpm: blocks per MCU
+  long long nblocks;
+  const unsigned char* scan;
+  long long scan_bytes;
+  const t3d_jpeg_seg* segs;
+  unsigned char* out;
+  short* coef;                   // [nblocks][64]
+  unsigned char* planes;         // [nblocks][64]: the component planes, raster, one behind the other
+};
+
+T3D_JPEG_LANE Geom geom(const unsigned char* data, long long data_bytes, const t3d_jpeg_info* info, const t3d_jpeg_seg* segs,
+                        long long total_segs, const t3d_jpeg_item& it, unsigned char* out, long long out_bytes, void* work,
+                        long long total_blocks) {
+  Geom g;
+  g.ok = false;
+  g.h = info->h, g.w = info->w, g.ncomp = info->ncomp, g.sampling = info->sampling;
+  g.mcus_x = info->mcus_x, g.mcus_y = info->mcus_y, g.seg_mcus = info->seg_mcus, g.nseg = info->nseg;
+  g.nmcu = g.bpm = 0, g.nblocks = 0, g.scan = nullptr, g.scan_bytes = 0, g.segs = nullptr, g.out = nullptr, g.coef = nullptr;
+  g.planes = nullptr;
+  if (g.h < 1 || g.w < 1 || g.h > 65535 || g.w > 65535) return g;
+  if (g.sampling != T3D_JPEG_GRAY && g.sampling != T3D_JPEG_444 && g.sampling != T3D_JPEG_420) return g;
+  if (g.ncomp != (g.sampling == T3D_JPEG_GRAY ? 1 : 3)) return g;
+  const int px = g.sampling == T3D_JPEG_420 ? 16 : 8;
+  if (g.mcus_x != (g.w + px - 1) / px || g.mcus_y != (g.h + px - 1) / px) return g;
+  g.nmcu = g.mcus_x * g.mcus_y;                                             // <= 8192 * 8192
+  if (g.seg_mcus < 1 || g.nseg != (int)(((long long)g.nmcu + g.seg_mcus - 1) / g.seg_mcus)) return g;
+  g.bpm = t3d_jpeg_mcu_blocks(g.sampling);
+  g.nblocks = (long long)g.nmcu * g.bpm;
+  for (int c = 0; c < g.ncomp; ++c)
+    if (info->comp_dc[c] > 1 || info->comp_ac[c] > 1) return g;
+  const long long so = info->scan_offset, sb = info->scan_bytes;
+  if (it.file_offset < 0 || it.file_bytes < 0 || it.file_offset > data_bytes || it.file_bytes > data_bytes - it.file_offset) return g;
+  if (so < 0 || sb < 0 || so > it.file_bytes || sb > it.file_bytes - so || sb > 0xFFFFFFFFll) return g;
+  if (it.seg_offset < 0 || it.seg_offset > total_segs || g.nseg > total_segs - it.seg_offset) return g;
+  const long long ob = (long long)g.h * g.w * 3;
+  if (it.out_offset < 0 || it.out_offset > out_bytes || ob > out_bytes - it.out_offset) return g;
+  if (it.block_offset < 0 || it.block_offset > total_blocks || g.nblocks > total_blocks - it.block_offset) return g;
+  g.scan = data + it.file_offset + so;
+  g.scan_bytes = sb;
+  g.segs = segs + it.seg_offset;
+  g.out = out + it.out_offset;
+  g.coef = reinterpret_cast<short*>(work) + it.block_offset * 64;
+  g.planes = reinterpret_cast<unsigned char*>(work) + total_blocks * 128 + it.block_offset * 64;
+  g.ok = true;
+  return g;
+}
+
+// component c of the image: the first of its blocks (its plane starts 64 bytes a block into `planes`) and its size in blocks
+struct Plane { long long first; int bw, bh; };
+T3D_JPEG_LANE Plane plane(const Geom& g, int c) {
+  Plane p;
+  const int f = g.sampling == T3D_JPEG_420 ? 2 : 1;
+  const long long luma = (long long)g.nmcu * f * f;
+  p.bw = g.mcus_x * (c == 0 ? f : 1), p.bh = g.mcus_y * (c == 0 ? f : 1);
+  p.first = c == 0 ? 0 : luma + (long long)(c - 1) * g.nmcu;
+  return p;
+}
+
+// ---- entropy ---------------------------------------------------------------------------------------------------------------
+// The scan from byte `pos` on: a 64-bit window (valid bits at its low end), refilled when 32 bits or fewer are left with up to
+// four stream bytes that were loaded together.  FF 00 is one data byte FF; FF + anything else, or the scan's end, stops the
+// reader for good: from there it feeds zero bits and does not advance.
+struct Bits {
+  const unsigned char* p;
+  unsigned int n, pos;
+  unsigned long long buf;
+  int cnt;
+  bool stopped;
+
+  T3D_JPEG_LANE unsigned int at(unsigned long long i) const { return i < n ? p[i] : 0xFFu; }      // (behind the scan: a marker)
+  T3D_JPEG_LANE void refill() {
+    while (cnt <= 32) {
+      if (stopped) {
+        buf <<= 32;
+        cnt += 32;
+        break;
+      }
+      unsigned int b[5];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) b[i] = at((unsigned long long)pos + i);
+      int used = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (used > i || stopped) continue;              // a stuffed 00 that went with its FF
+        if (b[i] == 0xFFu) {
+          if (b[i + 1] != 0u) {
+            stopped = true;
+            continue;
+          }
+          used = i + 2;
+        } else {
+          used = i + 1;
+        }
+        buf = (buf << 8) | b[i];
+        cnt += 8;
+      }
+      pos += used;
+    }
+  }
+  T3D_JPEG_LANE unsigned int peek16() const { return (unsigned int)(buf >> (cnt - 16)) & 0xFFFFu; }    // cnt >= 16
+  T3D_JPEG_LANE int get(int k) {                        // k <= 16 <= cnt
+    cnt -= k;
+    return (int)((unsigned int)(buf >> cnt) & ((1u << k) - 1u));
+  }
+};
+
+// Segment s of a checked image: its MCUs [s * seg_mcus, ...) decoded from the indexed position, the non-zero quantised
+// coefficients stored in natural order into the segment's own (zeroed) blocks.  tab: DC 0, DC 1, AC 0, AC 1.
+// -> false: a code that does not exist (or a run past the block); the rest of the segment's blocks stay zero.
+T3D_JPEG_LANE bool decode_segment(const Geom& g, const t3d_jpeg_huff* tab, const int dci[3], const int aci[3], int s) {
+  const unsigned char zigzag[64] = T3D_JPEG_ZIGZAG;
+  const t3d_jpeg_seg sg = g.segs[s];
+  if (sg.byte >= g.scan_bytes || sg.bit > 7) return false;
+  Bits br;
+  br.p = g.scan, br.n = (unsigned int)g.scan_bytes, br.pos = sg.byte, br.buf = 0, br.cnt = 0, br.stopped = false;
+  br.refill();
+  br.cnt -= sg.bit;                                     // (the first refill took at least one byte, or stopped and made 32 bits)
+  int pred[3] = {sg.pred[0], sg.pred[1], sg.pred[2]};
+  const int ybl = g.sampling == T3D_JPEG_420 ? 4 : 1;   // luma blocks of an MCU
+  const long long first1 = plane(g, 1).first, first2 = plane(g, 2).first;
+  const int m0 = s * g.seg_mcus, m1 = g.nmcu - m0 > g.seg_mcus ? m0 + g.seg_mcus : g.nmcu;      // s < nseg: m0 < nmcu <= 2^26
+  for (int m = m0; m < m1; ++m) {
+    const int my = m / g.mcus_x, mx = m - my * g.mcus_x;
+    for (int b = 0; b < g.bpm; ++b) {
+      const int c = b < ybl ? 0 : b - ybl + 1;
+      long long blk;
+      if (c == 0) blk = ybl == 4 ? (long long)(2 * my + (b >> 1)) * (2 * g.mcus_x) + 2 * mx + (b & 1) : (long long)m;
+      else blk = (c == 1 ? first1 : first2) + m;
+      short* dst = g.coef + blk * 64;                   // blk < nblocks: one of MCU m's own blocks
+      const t3d_jpeg_huff* hd = tab + dci[c];
+      const t3d_jpeg_huff* ha = tab + aci[c];
+      br.refill();
+      int e = t3d_jpeg_huff_decode(hd, br.peek16());
+      if (e < 0 || (e & 255) > 15) return false;
+      br.cnt -= e >> 8;
+      const int t = e & 255;
+      pred[c] = (int)((unsigned int)pred[c] + (unsigned int)t3d_jpeg_extend(br.get(t), t));      // (wraps; never overflows)
+      if (pred[c] != 0) dst[0] = (short)pred[c];
+      for (int k = 1; k < 64;) {                        // k grows by at least 1 a round
+        br.refill();
+        e = t3d_jpeg_huff_decode(ha, br.peek16());
+        if (e < 0) return false;
+        br.cnt -= e >> 8;
+        const int r = (e >> 4) & 15, sz = e & 15;
+        if (sz == 0) {
+          if (r != 15) break;
+          k += 16;
+          if (k > 64) return false;
+          continue;
+        }
+        k += r;
+        if (k > 63) return false;
+        dst[zigzag[k]] = (short)t3d_jpeg_extend(br.get(sz), sz);
+        ++k;
+      }
+    }
+  }
+  return true;
+}
+
+// ---- inverse DCT -----------------------------------------------------------------------------------------------------------
+// jpeg_idct_islow's butterfly on eight values; SHIFT: 11 (columns) or 18 (rows).  Unsigned arithmetic where a stream that no
+// encoder makes could overflow (it wraps, as the int32 definition says); the shifts are arithmetic.
+template <int SHIFT>
+T3D_JPEG_LANE void idct8(const int in[8], int o[8]) {
+  typedef unsigned int U;
+  U z2 = (U)in[2], z3 = (U)in[6];
+  U z1 = (z2 + z3) * 4433u;
+  U tmp2 = z1 - z3 * 15137u;
+  U tmp3 = z1 + z2 * 6270u;
+  z2 = (U)in[0], z3 = (U)in[4];
+  U tmp0 = (z2 + z3) << 13;
+  U tmp1 = (z2 - z3) << 13;
+  const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  tmp0 = (U)in[7], tmp1 = (U)in[5], tmp2 = (U)in[3], tmp3 = (U)in[1];
+  z1 = tmp0 + tmp3, z2 = tmp1 + tmp2, z3 = tmp0 + tmp2;
+  U z4 = tmp1 + tmp3;
+  const U z5 = (z3 + z4) * 9633u;
+  tmp0 *= 2446u, tmp1 *= 16819u, tmp2 *= 25172u, tmp3 *= 12299u;
+  z1 *= (U)-7373, z2 *= (U)-20995, z3 *= (U)-16069, z4 *= (U)-3196;
+  z3 += z5, z4 += z5;
+  tmp0 += z1 + z3, tmp1 += z2 + z4, tmp2 += z2 + z3, tmp3 += z1 + z4;
+  const U rnd = 1u << (SHIFT - 1);
+  o[0] = (int)(tmp10 + tmp3 + rnd) >> SHIFT;
+  o[7] = (int)(tmp10 - tmp3 + rnd) >> SHIFT;
+  o[1] = (int)(tmp11 + tmp2 + rnd) >> SHIFT;
+  o[6] = (int)(tmp11 - tmp2 + rnd) >> SHIFT;
+  o[2] = (int)(tmp12 + tmp1 + rnd) >> SHIFT;
+  o[5] = (int)(tmp12 - tmp1 + rnd) >> SHIFT;
+  o[3] = (int)(tmp13 + tmp0 + rnd) >> SHIFT;
+  o[4] = (int)(tmp13 - tmp0 + rnd) >> SHIFT;
+}
+
+// block blk of a checked image: dequantise (quant [3][64], natural order), both passes, 8 x 8 samples into its plane
+T3D_JPEG_LANE void idct_block(const Geom& g, const int* quant, long long blk) {
+  const Plane pl1 = plane(g, 1), pl2 = plane(g, 2);
+  const int c = blk < pl1.first || g.ncomp == 1 ? 0 : (blk < pl2.first ? 1 : 2);
+  const Plane pl = c == 0 ? plane(g, 0) : (c == 1 ? pl1 : pl2);
+  const int rel = (int)(blk - pl.first), by = rel / pl.bw, bx = rel - by * pl.bw;
+  const short* src = g.coef + blk * 64;
+  const int* q = quant + 64 * c;
+  int ws[64];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const Int4 v = *reinterpret_cast<const Int4*>(src + 8 * r);             // (work is 16-byte aligned, a block 128 bytes)
+    const int pair[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ws[8 * r + 2 * j] = (int)(short)(pair[j] & 0xFFFF) * q[8 * r + 2 * j];
+      ws[8 * r + 2 * j + 1] = (pair[j] >> 16) * q[8 * r + 2 * j + 1];
+    }
+  }
+#pragma unroll
+  for (int x = 0; x < 8; ++x) {                         // columns
+    int in[8], o[8];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) in[y] = ws[8 * y + x];
+    idct8<11>(in, o);
+#pragma unroll
+    for (int y = 0; y < 8; ++y) ws[8 * y + x] = o[y];
+  }
+  const long long stride = (long long)pl.bw * 8;
+  unsigned char* dst = g.planes + pl.first * 64 + (long long)by * 8 * stride + bx * 8;      // 8-byte aligned
+#pragma unroll
+  for (int y = 0; y < 8; ++y) {                         // rows
+    int o[8];
+    idct8<18>(ws + 8 * y, o);
+    UInt2 w;
+    w.x = w.y = 0;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      w.x |= (unsigned int)clamp255(o[x] + 128) << (8 * x);
+      w.y |= (unsigned int)clamp255(o[x + 4] + 128) << (8 * x);
+    }
+    *reinterpret_cast<UInt2*>(dst + y * stride) = w;
+  }
+}
+
+// ---- chroma upsampling and colour ------------------------------------------------------------------------------------------
+// one chroma sample of pixel (y, x) of a 4:2:0 image: s the plane (stride bytes a row), dh x dw real samples
+T3D_JPEG_LANE int up420(const unsigned char* s, long long stride, int dh, int dw, int y, int x) {
+  const int r = y >> 1, cx = x >> 1;
+  if (dw <= 2) return s[r * stride + cx];
+  const int r2 = (y & 1) ? lo(r + 1, dh - 1) : hi(r - 1, 0);
+  const unsigned char* a = s + r * stride;
+  const unsigned char* b = s + r2 * stride;
+  const int here = 3 * a[cx] + b[cx];
+  if (x & 1) {
+    if (cx == dw - 1) return (4 * here + 7) >> 4;
+    return (3 * here + 3 * a[cx + 1] + b[cx + 1] + 7) >> 4;
+  }
+  if (cx == 0) return (4 * here + 8) >> 4;
+  return (3 * here + 3 * a[cx - 1] + b[cx - 1] + 8) >> 4;
+}
+
+// pixel (y, x) of a checked image -> R, G, B
+T3D_JPEG_LANE void pixel(const Geom& g, int y, int x, int px[3]) {
+  const Plane pl0 = plane(g, 0), pl1 = plane(g, 1), pl2 = plane(g, 2);
+  const long long ystride = (long long)pl0.bw * 8, cstride = (long long)pl1.bw * 8;
+  const int Y = g.planes[y * ystride + x];
+  if (g.ncomp == 1) {
+    px[0] = px[1] = px[2] = Y;
+    return;
+  }
+  const unsigned char* pcb = g.planes + pl1.first * 64;
+  const unsigned char* pcr = g.planes + pl2.first * 64;
+  int cb, cr;
+  if (g.sampling == T3D_JPEG_420) {
+    const int dh = (g.h + 1) >> 1, dw = (g.w + 1) >> 1;
+    cb = up420(pcb, cstride, dh, dw, y, x);
+    cr = up420(pcr, cstride, dh, dw, y, x);
+  } else {
+    cb = pcb[y * cstride + x];
+    cr = pcr[y * cstride + x];
+  }
+  cb -= 128, cr -= 128;
+  px[0] = clamp255(Y + ((91881 * cr + 32768) >> 16));
+  px[1] = clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+  px[2] = clamp255(Y + ((116130 * cb + 32768) >> 16));
+}
+
+// run t of a checked image: its pixels 4t .. 4t + 3, as three dwords where the image is dword aligned and the run whole
+T3D_JPEG_LANE void colour_run(const Geom& g, long long t, bool aligned) {
+  const long long npix = (long long)g.h * g.w, r0 = 4 * t;
+  // (h, w <= 65535: a pixel index fits 32 bits unsigned -- one 32-bit division a run, then steps)
+  int y = (int)((unsigned int)r0 / (unsigned int)g.w), x = (int)((unsigned int)r0 - (unsigned int)y * (unsigned int)g.w);
+  if (aligned && r0 + 4 <= npix) {
+    unsigned int word[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      int px[3];
+      pixel(g, y, x, px);
+      if (++x == g.w) x = 0, ++y;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int b = 3 * k + c;
+        word[b >> 2] |= (unsigned int)px[c] << (8 * (b & 3));
+      }
+    }
+    unsigned int* o4 = reinterpret_cast<unsigned int*>(g.out + 3 * r0);
+    o4[0] = word[0], o4[1] = word[1], o4[2] = word[2];
+  } else {
+    for (long long r = r0; r < lo(r0 + 4, npix); ++r) {
+      int px[3];
+      pixel(g, y, x, px);
+      if (++x == g.w) x = 0, ++y;
+      g.out[3 * r] = (unsigned char)px[0], g.out[3 * r + 1] = (unsigned char)px[1], g.out[3 * r + 2] = (unsigned char)px[2];
+    }
+  }
+}
+
+}  // namespace t3d_jpeg_lane

@@ -90,6 +90,9 @@ SIGNATURES = {
     't3d_augment_chain_crops_u8': [_P, _L, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P],
     't3d_augment_chain_resized_u8': [_P, _L, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P],
     't3d_detect_augment_u8': [_P, _L, _P, _P, _I, _I, _I, _P],
+    't3d_jpeg_index': [_P, _L, _I, _P, _P, _L],
+    't3d_jpeg_decode_work_bytes': [_L, ctypes.POINTER(_L)],
+    't3d_jpeg_decode_u8': [_P, _L, _P, _P, _L, _P, _P, _L, _P, _L, _L, _P, _I, _I, _I, _P],
     't3d_pwconv_fwd_mat': [_I, _P, _PP, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     't3d_ssd_decode_nms': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P],
     't3d_ssd_multibox_work_bytes': [_I, _I],

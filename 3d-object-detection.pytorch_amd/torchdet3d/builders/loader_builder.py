@@ -100,7 +100,10 @@ def build_detection_loader(cfg):
     """The detector's loaders from an mmdet-style config object (the shape of configs/detection/mnv2_ssd_300_2_heads.py:63-143;
     attributes or keys): `input_size`, `train_pipeline`, `test_pipeline`, `data.samples_per_gpu`, `data.workers_per_gpu`,
     `data.train.dataset.{ann_file, img_prefix, min_size, classes}` (a `RepeatDataset` wrapper with times=1; `data.train` itself
-    may also be the dataset), `data.val.{ann_file, img_prefix}`; optional `seed`.  -> (train, val) `GpuDetectionLoader`s:
+    may also be the dataset), `data.val.{ann_file, img_prefix}`; optional `seed`; optional `data.decode` ('host', the default: Pillow in the workers; 'device':
+    the workers read file bytes and the frames are decoded on the GPU, dataloaders/jpeg.py), `data.decode_index` (a path stem:
+    the JPEG indexes are kept in `<stem>.train.npy` / `<stem>.val.npy`, built when missing) and `data.decode_seg_mcus`.
+    -> (train, val) `GpuDetectionLoader`s:
     train yields (imgs uint8 [B,S,S,3], gt_boxes, gt_labels, gt_counts), shuffled by (seed, epoch), last partial batch dropped;
     val is the test pipeline (the resize alone) in dataset order and also yields ori_shapes.  `samples_per_gpu` is PER RANK,
     as in mmdet; under several ranks train uses a DistributedSampler over the one dataset every rank holds and val walks the
@@ -123,12 +126,20 @@ def build_detection_loader(cfg):
     if test_tf.random:
         raise NotImplementedError('test_pipeline: only the Resize alone is built')
     world, rk = world_size(), rank()
-    ds = ObjectronFrames(_get(tr, 'img_prefix'), 'train', cats, int(_get(tr, 'min_size', 17) or 0), ann_file=_get(tr, 'ann_file'))
+    decode = _get(data, 'decode', 'host')
+    stem, seg_mcus = _get(data, 'decode_index'), _get(data, 'decode_seg_mcus')
+
+    def indexed(d, which):
+        if decode == 'device':
+            d.build_index(None if stem is None else f'{stem}.{which}.npy', threads=16, seg_mcus=seg_mcus)
+        return d
+    ds = indexed(ObjectronFrames(_get(tr, 'img_prefix'), 'train', cats, int(_get(tr, 'min_size', 17) or 0),
+                                 ann_file=_get(tr, 'ann_file'), decode=decode), 'train')
     sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rk, shuffle=True, seed=seed,
                                                               drop_last=True)
     train = GpuDetectionLoader(ds, train_tf, bs, sampler=sampler, num_workers=nw, drop_last=True, seed=seed, rank=rk)
     va = _get(data, 'val')
-    dv = ObjectronFrames(_get(va, 'img_prefix'), 'val', cats, ann_file=_get(va, 'ann_file'))
+    dv = indexed(ObjectronFrames(_get(va, 'img_prefix'), 'val', cats, ann_file=_get(va, 'ann_file'), decode=decode), 'val')
     if world > 1:
         dv = torch.utils.data.Subset(dv, range(rk, len(dv), world))
     val = GpuDetectionLoader(dv, test_tf, bs, num_workers=nw, seed=seed, rank=rk)

@@ -22,6 +22,7 @@ it here, so the step compiles to nothing); the kernel rounds (half to even) and 
 """
 import itertools
 import json
+import os
 from pathlib import Path
 
 import numpy as np
@@ -53,12 +54,19 @@ class ObjectronFrames(torch.utils.data.Dataset):
     OBJECTRON_CLASSES; 'all' keeps every one; the label stays category_id - 1, it is not renumbered); in train mode an image
     is dropped when no box is left or when min(width, height) < min_size.
     Index: the images that survive, in the order of the json's 'images' list -- dataset index i is the i-th of them, whatever
-    their ids are; `image_ids[i]` is its id."""
+    their ids are; `image_ids[i]` is its id.
 
-    def __init__(self, root, mode='train', category_list='all', min_size=17, ann_file=None):
+    decode='device' (dataloaders/jpeg.py): after `build_index()` an item is (the FILE's bytes uint8 [n], boxes, labels, i) and
+    the frame is decoded on the device by `GpuDetectionLoader`; for a file the index keeps on the host (progressive, restart
+    markers, 4:2:2, not a JPEG, ...) the payload is the host-decoded frame [h, w, 3] instead.  The workers then only read
+    files; they never touch the native library."""
+
+    def __init__(self, root, mode='train', category_list='all', min_size=17, ann_file=None, decode='host'):
         if mode not in ('train', 'val', 'test'):
             raise RuntimeError('Unknown dataset mode')
-        self.root, self.mode = str(root), mode
+        if decode not in ('host', 'device'):
+            raise ValueError(f"decode={decode!r}: 'host' or 'device'")
+        self.root, self.mode, self.decode, self.index = str(root), mode, decode, None
         if ann_file is None:
             ann_file = Path(root).resolve() / ('annotations/objectron_train.json' if mode == 'train'
                                                else 'annotations/objectron_test.json')
@@ -96,10 +104,43 @@ class ObjectronFrames(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.files)
 
+    def build_index(self, path=None, threads=8, seg_mcus=None):
+        """The JPEG index `decode='device'` needs, like `fill_cache()` on the regression side: loaded from `path` when that file
+        exists (memory-mapped; every file's size and mtime are checked against it and a changed file raises, naming it), else
+        built with `threads` host threads of this process and, with a `path`, saved there.  -> the `JpegIndex`."""
+        from .jpeg import DEFAULT_SEG_MCUS, JpegIndex
+        if path is not None and os.path.exists(path):
+            index = JpegIndex.load(path, mmap_mode='r' if not str(path).endswith('.npz') else None)
+            if index.files != self.files:
+                raise RuntimeError(f'{path} indexes other files than this dataset holds: rebuild the index')
+            if seg_mcus is not None and index.seg_mcus != int(seg_mcus):
+                raise RuntimeError(f'{path} was built with seg_mcus = {index.seg_mcus}, not {seg_mcus}: rebuild the index')
+            index.check(self.root)
+        else:
+            index = JpegIndex.build(self.files, self.root, seg_mcus or DEFAULT_SEG_MCUS, threads)
+            if path is not None:
+                index.save(path)
+        self.index = index
+        return index
+
+    def _decode_host(self, path):
+        with Image.open(path) as im:
+            return np.asarray(im.convert('RGB'))
+
     def __getitem__(self, i):
-        with Image.open(self.root + '/' + self.files[i]) as im:
-            frame = np.asarray(im.convert('RGB'))
-        return frame, self._boxes[i].copy(), self._labels[i].copy()
+        path = self.root + '/' + self.files[i]
+        if self.decode == 'host':
+            return self._decode_host(path), self._boxes[i].copy(), self._labels[i].copy()
+        if self.index is None:
+            raise RuntimeError("ObjectronFrames(decode='device'): call build_index() first")
+        if int(self.index.reason[i]) != 0:
+            payload = self._decode_host(path)
+        else:
+            payload = np.fromfile(path, np.uint8)
+            if payload.size != int(self.index.size[i]):
+                raise RuntimeError(f'{path} changed since it was indexed ({payload.size} bytes now, {int(self.index.size[i])} in '
+                                   f'the index): rebuild the index')
+        return payload, self._boxes[i].copy(), self._labels[i].copy(), i
 
 
 def collate_frames(items):

@@ -20,6 +20,12 @@ such sampler repeats its augmentations every epoch, as `GpuAugmentLoader` does.
 There is no device cache here: a 1920 x 1440 frame is 8 MB, the train set would need terabytes, and every epoch crops
 another part of the frame.  Measured: the launch takes 0.1 ms for 80 frames of 1440 x 1920, their
 upload 11.6 ms, their Pillow decode 658 ms of one host core -- the workers' JPEG decode is what bounds this loader.
+
+Over `ObjectronFrames(decode='device')` (dataloaders/jpeg.py) the workers return file bytes instead (`collate_jpeg`); `finish`
+then uploads the bytes, puts the batch's index rows into the one pinned copy, allocates the packed frame buffer on the device,
+copies the frames of files the index keeps on the host into their slots and calls `t3d_jpeg_decode_u8` on the same stream in
+front of the augment launch.  The frame table comes from the index; prefetch, staging rotation, keys and the yielded tuple are
+the same, and so are the batches, bit for bit.  `last_status` is the device status vector of the last decode call.
 """
 import collections
 
@@ -28,6 +34,7 @@ import torch
 
 from .. import _native as N
 from .detection import collate_frames
+from .jpeg import collate_jpeg, launch_decode, plan_batch
 from .objectron import AUG_SAMPLE_DTYPE
 
 __all__ = ['GpuDetectionLoader']
@@ -39,9 +46,14 @@ class GpuDetectionLoader:
     def __init__(self, dataset, pipeline, batch_size, sampler=None, shuffle=False, num_workers=0, drop_last=False, seed=0,
                  rank=0, prefetch=1):
         self.pipeline, self.seed, self.rank, self.prefetch = pipeline, int(seed), int(rank), int(prefetch)
+        # ObjectronFrames(decode='device') -- directly or under a Subset: byte items, decoded in `finish` (dataloaders/jpeg.py)
+        self._frames = getattr(dataset, 'dataset', dataset)
+        self.decode = getattr(self._frames, 'decode', 'host')
+        self.last_status = None         # device int32 [files decoded on the device] of the last batch's t3d_jpeg_decode_u8
         self.loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, sampler=sampler,
                                                   shuffle=shuffle if sampler is None else False,
-                                                  num_workers=int(num_workers or 0), collate_fn=collate_frames,
+                                                  num_workers=int(num_workers or 0),
+                                                  collate_fn=collate_jpeg if self.decode == 'device' else collate_frames,
                                                   pin_memory=torch.cuda.is_available(), drop_last=drop_last)
         self.dataset, self.batch_size = dataset, batch_size
         self._slots = [[None, None] for _ in range(self.NBUF)]     # (pinned host buffer, event after its upload)
@@ -95,12 +107,27 @@ class GpuDetectionLoader:
         """One host batch -> the device tuple, enqueued on the copy stream (prefetch >= 1: the ready event is appended) or on
         the current stream (prefetch 0)."""
         prefetch = self.prefetch if prefetch is None else prefetch
-        packed = host_batch[0]
+        packed, plan, fallback = host_batch[0], None, ()
+        if self.decode == 'device':
+            # byte items: the frame table comes from the index, the frames themselves are decoded below, on the device
+            table, index = host_batch[1].numpy(), self._frames.index
+            on_dev = np.flatnonzero(table[:, 1] == 0)
+            desc = np.zeros((len(table), 3), np.int64)
+            desc[:, 1:] = table[:, 3:5]
+            desc[on_dev, 1], desc[on_dev, 2] = index.infos['h'][table[on_dev, 0]], index.infos['w'][table[on_dev, 0]]
+            frame_bytes = desc[:, 1] * desc[:, 2] * 3
+            desc[:, 0] = np.cumsum(frame_bytes) - frame_bytes              # the layout collate_frames packs
+            if len(on_dev):
+                plan = plan_batch([index.rows(int(i)) for i in table[on_dev, 0]], table[on_dev, 2], table[on_dev, 3], desc[on_dev, 0])
+            fallback = [(int(table[k, 2]), int(desc[k, 0]), int(frame_bytes[k])) for k in np.flatnonzero(table[:, 1] == 1)]
+            host_batch = (packed, torch.from_numpy(desc)) + tuple(host_batch[2:])
         rec, gb, gl, gc, shapes = self.host_batch(host_batch, key_tail)
         B, G = gb.shape[:2]
         oh, ow = self.pipeline.size
         parts = [rec.view(np.uint8), gb.reshape(-1).view(np.uint8), gl.reshape(-1).view(np.uint8), gc.view(np.uint8),
                  shapes.reshape(-1).view(np.uint8)]
+        if plan is not None:                   # the batch's index rows ride in the same pinned copy
+            parts += [plan['infos'].view(np.uint8), plan['segs'].view(np.uint8), plan['items'].view(np.uint8)]
         offs = np.concatenate([[0], np.cumsum([(p.size + 7) // 8 * 8 for p in parts])])      # each part 8-byte aligned
         total = int(offs[-1])
         slot = self._staging(total)
@@ -120,6 +147,13 @@ class GpuDetectionLoader:
             slot[1].record(stream)
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
             src = packed.to(dev, non_blocking=True)
+            if self.decode == 'device':
+                raw, src = src, torch.empty(max(int(frame_bytes.sum()), 1), dtype=torch.uint8, device=dev)
+                for at, to, n in fallback:     # frames the host had to decode go to their slots as they are
+                    src[to:to + n].copy_(raw[at:at + n], non_blocking=True)
+                if plan is not None:
+                    tabs = [meta[offs[k]:offs[k] + parts[k].size] for k in (5, 6, 7)]
+                    self.last_status = launch_decode(raw, *tabs, plan, src)
             N.call('t3d_detect_augment_u8' if self.pipeline.random else 't3d_augment_crops_u8', N.ptr(src), src.numel(),
                    N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
 

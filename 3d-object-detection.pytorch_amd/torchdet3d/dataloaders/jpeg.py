@@ -1,0 +1,232 @@
+"""JPEG frames decoded on the device from a per-file MCU index (include/t3d.h next to t3d_jpeg_index; csrc/jpeg_index.h,
+csrc/jpeg.hip).
+
+Baseline Huffman decoding is serial inside a scan and Objectron frames carry no restart markers, so the work is split the way
+the crop cache splits the regression loader's: ONCE PER FILE `JpegIndex.build` walks every scan on the host (a thread pool in
+the main process -- ctypes releases the GIL; no DataLoader worker ever loads the library) and records where every
+`seg_mcus`-th MCU starts; EVERY EPOCH the workers only read file bytes and `t3d_jpeg_decode_u8` decodes all segments of all
+frames of a batch in parallel into the packed frame buffer `t3d_detect_augment_u8` reads (`GpuDetectionLoader`,
+`ObjectronFrames(decode='device')`).  The pixels are those of Pillow on libjpeg-turbo, bit for bit.
+
+A file the device path does not take (progressive, restart markers, 4:2:2, CMYK, ... or malformed) keeps its reason in the
+index and is decoded on the host as before.
+
+`decode_jpeg_batch(files, rows)` is the one-call form: a list of file contents and their index rows -> the packed device
+buffer and its descriptor table, the layout `collate_frames` produces."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+__all__ = ['JpegIndex', 'decode_jpeg_batch', 'index_jpeg', 'collate_jpeg', 'INFO_DTYPE', 'SEG_DTYPE', 'ITEM_DTYPE',
+           'DEFAULT_SEG_MCUS', 'REASONS']
+
+# include/t3d.h: t3d_jpeg_info (864 bytes), t3d_jpeg_seg (16), t3d_jpeg_item (48)
+INFO_DTYPE = np.dtype([('h', '<i4'), ('w', '<i4'), ('ncomp', '<i4'), ('sampling', '<i4'), ('mcus_x', '<i4'), ('mcus_y', '<i4'),
+                       ('seg_mcus', '<i4'), ('nseg', '<i4'), ('scan_offset', '<i8'), ('scan_bytes', '<i8'), ('reason', '<i4'),
+                       ('reserved', '<i4'), ('comp_dc', 'u1', (4,)), ('comp_ac', 'u1', (4,)), ('quant', 'u1', (3, 64)),
+                       ('dc_bits', 'u1', (2, 16)), ('dc_vals', 'u1', (2, 16)), ('ac_bits', 'u1', (2, 16)), ('ac_vals', 'u1', (2, 256))])
+SEG_DTYPE = np.dtype([('byte', '<u4'), ('pred', '<i2', (3,)), ('bit', 'u1'), ('reserved', 'u1'), ('mcu', '<i4')])
+ITEM_DTYPE = np.dtype([('file_offset', '<i8'), ('file_bytes', '<i8'), ('out_offset', '<i8'), ('block_offset', '<i8'),
+                       ('seg_offset', '<i8'), ('reserved', '<i8')])
+assert INFO_DTYPE.itemsize == 864 and SEG_DTYPE.itemsize == 16 and ITEM_DTYPE.itemsize == 48
+# MCUs per segment = per device lane.  tools/time_jpeg_decode.py sweeps 2 .. 120: the best of the sweep
+DEFAULT_SEG_MCUS = 2
+# why a file stays on the host decode: T3D_JPEG_REASON_* of include/t3d.h, and -1 for a file the indexer calls malformed
+REASONS = {0: 'decoded on the device', 1: 'not a baseline frame (progressive, extended, lossless or arithmetic)',
+           2: 'sample precision other than 8 bit', 3: 'restart interval', 4: 'sampling other than 4:4:4 / 4:2:0',
+           5: 'component count other than 1 or 3', 6: 'more than one scan', 7: '16-bit quantisation table',
+           8: 'three components that are not YCbCr', -1: 'malformed'}
+_BLOCKS_PER_MCU = (1, 3, 6)             # gray, 4:4:4, 4:2:0
+_MAGIC = 0x7833644A50454731             # 'x3dJPEG1'
+
+
+def index_jpeg(data, seg_mcus=DEFAULT_SEG_MCUS):
+    """One file's bytes -> (return code of t3d_jpeg_index, info record, segment table).  Host only: no GPU is touched."""
+    from .. import _native as N
+    lib = N.lib()
+    a = np.frombuffer(data, np.uint8)
+    info = np.zeros(1, INFO_DTYPE)
+    rc = lib.t3d_jpeg_index(a.ctypes.data, a.size, int(seg_mcus), info.ctypes.data, None, 0)
+    segs = np.zeros(int(info['nseg'][0]) if rc == 0 else 0, SEG_DTYPE)
+    if rc == 0:
+        rc = lib.t3d_jpeg_index(a.ctypes.data, a.size, int(seg_mcus), info.ctypes.data, segs.ctypes.data, len(segs))
+    return rc, info[0], segs
+
+
+class JpegIndex:
+    """The index of a list of files, as flat numpy arrays: `infos` [n] INFO_DTYPE, `segs` [total] SEG_DTYPE, `seg_start` int64
+    [n + 1] (file i owns segs[seg_start[i]:seg_start[i + 1]]), `size` and `mtime_ns` int64 [n] of the file when it was indexed,
+    `reason` int64 [n] (0: the device decodes it; REASONS), `files` (the names, relative to the root)."""
+
+    def __init__(self, files, infos, segs, seg_start, size, mtime_ns, reason, seg_mcus):
+        self.files, self.infos, self.segs, self.seg_start = list(files), infos, segs, seg_start
+        self.size, self.mtime_ns, self.reason, self.seg_mcus = size, mtime_ns, reason, int(seg_mcus)
+
+    def __len__(self):
+        return len(self.files)
+
+    @classmethod
+    def build(cls, files, root, seg_mcus=DEFAULT_SEG_MCUS, threads=8):
+        """Index `files` (names relative to `root`) with `threads` <= 16 host threads of THIS process."""
+        from .. import _native as N
+        N.lib()                                     # (load it once, before the threads ask for it)
+        threads = max(1, min(int(threads), 16))
+
+        def one(name):
+            path = os.path.join(str(root), name)
+            st = os.stat(path)
+            rc, info, segs = index_jpeg(np.fromfile(path, np.uint8), seg_mcus)
+            reason = 0 if rc == 0 else (int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1)
+            return info, segs, st.st_size, st.st_mtime_ns, reason
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            rows = list(ex.map(one, files))
+        infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
+        seg_start = np.concatenate([[0], np.cumsum([len(r[1]) for r in rows])]).astype(np.int64)
+        segs = np.concatenate([r[1] for r in rows] + [np.zeros(0, SEG_DTYPE)])
+        return cls(files, infos, segs, seg_start, np.array([r[2] for r in rows], np.int64), np.array([r[3] for r in rows], np.int64),
+                   np.array([r[4] for r in rows], np.int64), seg_mcus)
+
+    def rows(self, i):
+        """-> (info record, segment table) of file i: what `decode_jpeg_batch` takes."""
+        return self.infos[i], self.segs[self.seg_start[i]:self.seg_start[i + 1]]
+
+    def check(self, root, i=None):
+        """Raises RuntimeError naming the first file (or file i) whose size or mtime is no longer what was indexed."""
+        for k in (range(len(self.files)) if i is None else [i]):
+            path = os.path.join(str(root), self.files[k])
+            st = os.stat(path)
+            if st.st_size != int(self.size[k]) or st.st_mtime_ns != int(self.mtime_ns[k]):
+                raise RuntimeError(f'{path} changed since it was indexed (size {st.st_size} / mtime {st.st_mtime_ns} now, '
+                                   f'{int(self.size[k])} / {int(self.mtime_ns[k])} in the index): rebuild the index')
+
+    # ---- one flat uint8 array on disk: .npy (loadable with mmap_mode='r') or .npz ----
+    def _sections(self):
+        names = np.frombuffer('\n'.join(self.files).encode(), np.uint8)
+        return [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in
+                (self.infos, self.segs, self.seg_start, self.size, self.mtime_ns, self.reason, names)]
+
+    def save(self, path):
+        sec = self._sections()
+        head = np.array([_MAGIC, len(self.files), len(self.segs), self.seg_mcus, sec[-1].size, 0, 0, 0], np.int64)
+        parts, off = [head.view(np.uint8)], 64
+        for s in sec:
+            pad = -s.size % 64
+            parts += [s, np.zeros(pad, np.uint8)]
+            off += s.size + pad
+        blob = np.concatenate(parts)
+        path = str(path)
+        if path.endswith('.npz'):
+            np.savez(path, index=blob)
+        else:
+            with open(path, 'wb') as f:             # (np.save would append '.npy' to another suffix)
+                np.save(f, blob)
+
+    @classmethod
+    def load(cls, path, mmap_mode=None):
+        path = str(path)
+        blob = np.load(path)['index'] if path.endswith('.npz') else np.load(path, mmap_mode=mmap_mode)
+        head = np.asarray(blob[:64]).view(np.int64)
+        if blob.dtype != np.uint8 or int(head[0]) != _MAGIC:
+            raise RuntimeError(f'{path} is not a JPEG index')
+        n, total, seg_mcus, nb = (int(v) for v in head[1:5])
+        out, off = [], 64
+        for dt, cnt in ((INFO_DTYPE, n), (SEG_DTYPE, total), (np.int64, n + 1), (np.int64, n), (np.int64, n), (np.int64, n),
+                        (np.uint8, nb)):
+            size = np.dtype(dt).itemsize * cnt
+            out.append(blob[off:off + size].view(dt))
+            off += size + -size % 64
+        files = bytes(np.asarray(out[6])).decode().split('\n') if n else []
+        return cls(files, *out[:6], seg_mcus)
+
+
+def collate_jpeg(items):
+    """DataLoader collate of `ObjectronFrames(decode='device')` items (payload, boxes, labels, i): the payloads -- file bytes, or
+    a host-decoded frame for a file the index keeps on the host -- in one uint8 buffer with a table.
+    -> (blob uint8 [bytes], table int64 [B, 5] = (dataset index, 0 bytes / 1 frame, offset in blob, bytes or h, 0 or w),
+    boxes float32 [sum n, 4], labels int32 [sum n], counts int64 [B])."""
+    import torch
+    table = np.zeros((len(items), 5), np.int64)
+    off = 0
+    for k, (p, _, _, i) in enumerate(items):
+        table[k] = (i, 1, off, p.shape[0], p.shape[1]) if p.ndim == 3 else (i, 0, off, p.size, 0)
+        off += p.size
+    blob = np.empty(max(off, 1), np.uint8)
+    for (p, _, _, _), row in zip(items, table):
+        blob[row[2]:row[2] + p.size] = p.reshape(-1)
+    boxes = np.concatenate([np.asarray(b, np.float32).reshape(-1, 4) for _, b, _, _ in items])
+    labels = np.concatenate([np.asarray(l, np.int32).reshape(-1) for _, _, l, _ in items])
+    counts = np.asarray([len(l) for _, _, l, _ in items], np.int64)
+    return (torch.from_numpy(blob), torch.from_numpy(table), torch.from_numpy(boxes), torch.from_numpy(labels),
+            torch.from_numpy(counts))
+
+
+def plan_batch(rows, file_offsets, file_sizes, out_offsets):
+    """The tables of one t3d_jpeg_decode_u8 call: rows [(info, segs)] of the batch's files, where each file's bytes lie in
+    the data buffer and where its frame goes.  -> dict(infos, segs, items (numpy, to upload), total_segs, total_blocks,
+    max_segs, max_blocks)."""
+    infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
+    segs = np.concatenate([np.asarray(r[1]) for r in rows] + [np.zeros(0, SEG_DTYPE)])
+    for inf, s in zip(infos, (r[1] for r in rows)):
+        if int(inf['reason']) or int(inf['nseg']) != len(s) or int(inf['nseg']) < 1:
+            raise ValueError('an index row of a file the device does not decode (its reason is set, or its table is incomplete)')
+    blocks = infos['mcus_x'].astype(np.int64) * infos['mcus_y'] * np.asarray(_BLOCKS_PER_MCU, np.int64)[infos['sampling']]
+    items = np.zeros(len(rows), ITEM_DTYPE)
+    items['file_offset'], items['file_bytes'], items['out_offset'] = file_offsets, file_sizes, out_offsets
+    items['block_offset'] = np.cumsum(blocks) - blocks
+    items['seg_offset'] = np.cumsum(infos['nseg'].astype(np.int64)) - infos['nseg']
+    return dict(infos=infos, segs=segs, items=items, total_segs=len(segs), total_blocks=int(blocks.sum()),
+                max_segs=int(infos['nseg'].max()), max_blocks=int(blocks.max()))
+
+
+def launch_decode(data, infos, segs, items, plan, out):
+    """Enqueue t3d_jpeg_decode_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items: device uint8
+    tensors holding plan['infos'], ['segs'], ['items'].  -> status, device int32 [B] (0: decoded to the last MCU)."""
+    import ctypes
+
+    import torch
+
+    from .. import _native as N
+    B = len(plan['infos'])
+    nbytes = ctypes.c_longlong(0)
+    if N.lib().t3d_jpeg_decode_work_bytes(plan['total_blocks'], ctypes.byref(nbytes)) != 0:
+        raise RuntimeError('t3d_jpeg_decode_work_bytes failed')
+    work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=out.device)
+    status = torch.empty(max(B, 1), dtype=torch.int32, device=out.device)
+    N.call('t3d_jpeg_decode_u8', N.ptr(data), data.numel(), N.ptr(infos), N.ptr(segs), plan['total_segs'], N.ptr(items), N.ptr(out),
+           out.numel(), N.ptr(work), work.numel(), plan['total_blocks'], N.ptr(status), B, plan['max_segs'], plan['max_blocks'],
+           N.stream())
+    return status[:B]
+
+
+def decode_jpeg_batch(files, rows, device=None):
+    """files: the contents of B JPEG files (bytes or uint8 arrays); rows: their index rows, [(info, segs)] from `JpegIndex.rows`
+    or `index_jpeg` -> (packed device uint8 [sum h * w * 3], desc int64 [B, 3] = (offset, h, w)): the frames as RGB [h][w][3],
+    the buffer and table `collate_frames` produces.  One t3d_jpeg_decode_u8 call on the current stream; nothing is read back
+    (`decode_jpeg_batch.last_status` holds the call's device status vector)."""
+    import torch
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    arrs = [np.frombuffer(f, np.uint8) for f in files]
+    B = len(arrs)
+    desc = np.zeros((B, 3), np.int64)
+    for i, (inf, _) in enumerate(rows):
+        desc[i, 1], desc[i, 2] = int(inf['h']), int(inf['w'])
+    frame_bytes = desc[:, 1] * desc[:, 2] * 3
+    desc[:, 0] = np.cumsum(frame_bytes) - frame_bytes
+    out = torch.empty(max(int(frame_bytes.sum()), 1), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return out, desc
+    sizes = np.array([a.size for a in arrs], np.int64)
+    plan = plan_batch(rows, np.cumsum(sizes) - sizes, sizes, desc[:, 0])
+    parts = [np.concatenate(arrs), plan['infos'].view(np.uint8), plan['segs'].view(np.uint8), plan['items'].view(np.uint8)]
+    offs = np.concatenate([[0], np.cumsum([-(-p.size // 16) * 16 for p in parts])])
+    host = np.zeros(int(offs[-1]), np.uint8)
+    for p, o in zip(parts, offs):
+        host[o:o + p.size] = p
+    d = torch.from_numpy(host).to(dev)
+    data, infos, segs, items = (d[o:o + p.size] for p, o in zip(parts, offs))
+    decode_jpeg_batch.last_status = launch_decode(data, infos, segs, items, plan, out)
+    return out, desc
+
+
+decode_jpeg_batch.last_status = None

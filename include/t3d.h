@@ -400,6 +400,100 @@ typedef struct {
 int t3d_detect_augment_u8(const unsigned char* src, long long src_bytes, const void* records, unsigned char* out, int B, int oh,
                           int ow, void* stream);
 
+/* Baseline JPEG frames decoded on the device from a per-file index (csrc/jpeg_index.h, csrc/jpeg.hip; replaces the workers'
+ * Pillow decode in front of t3d_detect_augment_u8).  Huffman decoding is serial inside a scan and Objectron frames carry no
+ * restart markers, so ONCE PER FILE the host walks the scan (t3d_jpeg_index) and records where every seg_mcus-th MCU starts;
+ * every epoch the device decodes all segments of all frames of a batch in parallel (t3d_jpeg_decode_u8).
+ *
+ * Supported: baseline sequential (SOF0), 8 bit, ONE interleaved scan, no restart interval, one component (gray) or three with
+ * sampling 1x1/1x1/1x1 (4:4:4) or 2x2/1x1/1x1 (4:2:0), YCbCr.  Anything else is T3D_ERR_UNSUPPORTED with info->reason set;
+ * malformed input (bad lengths, missing tables, a code that does not exist, a run past coefficient 63, a marker or the end of
+ * the data inside the scan, no EOI behind it) is T3D_ERR_ARG.  The indexer decodes the whole scan: a file it accepts is
+ * decodable to its last MCU, and the device is only ever given such files.
+ *
+ * DEFINITION (libjpeg / libjpeg-turbo's default path: JDCT_ISLOW, fancy upsampling; restated in numpy by tests/jpeg_ref.py;
+ * bit-exact against Pillow on libjpeg-turbo for streams whose dequantised coefficients fit int16 -- every encoder-made file;
+ * outside that libjpeg's own SIMD and C paths differ and the int32 arithmetic below is the definition):
+ *   entropy    baseline Huffman.  DC: category t, t more bits v, diff = v < 2^(t-1) ? v - 2^t + 1 : v, added to the component's
+ *              predictor.  AC: symbol run/size; 15/0 skips 16 coefficients, 0/0 ends the block; the value is extended like the
+ *              DC difference.  Coefficients arrive in zig-zag order and are stored in natural order.
+ *   IDCT       on coef * quant in int32, jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2, constants 2446 3196 4433 6270 7373 9633
+ *              12299 15137 16069 16819 20995 25172, the even / odd butterfly; columns first, descaled (x + 2^10) >> 11, then
+ *              rows, descaled (x + 2^17) >> 18 (arithmetic shifts), + 128, clamped to 0..255.
+ *   4:2:0      chroma has dh = ceil(h/2) x dw = ceil(w/2) real samples s; the padding of the last MCU is never read.  dw > 2:
+ *              output row 2r + v uses colsum[x] = 3 s[r][x] + s[r'][x], r' = max(r-1, 0) for v = 0, min(r+1, dh-1) for v = 1;
+ *              out[2x] = (3 colsum[x] + colsum[x-1] + 8) >> 4, out[2x+1] = (3 colsum[x] + colsum[x+1] + 7) >> 4, at the edges
+ *              out[0] = (4 colsum[0] + 8) >> 4, out[2dw-1] = (4 colsum[dw-1] + 7) >> 4.  dw <= 2: out[y][x] = s[y/2][x/2].
+ *   colour     FIX(x) = int(x * 65536 + 0.5), cb' = cb - 128, cr' = cr - 128:  R = y + ((FIX(1.402) cr' + 32768) >> 16),
+ *              B = y + ((FIX(1.772) cb' + 32768) >> 16), G = y + ((-FIX(0.34414) cb' + 32768 - FIX(0.71414) cr') >> 16), each
+ *              clamped to 0..255.  Gray: R = G = B = y.
+ *
+ * t3d_jpeg_index (HOST ONLY: no HIP call, never initialises the GPU; every read is checked against `bytes`): fills *info, and
+ * -- when segs != NULL -- one t3d_jpeg_seg per seg_mcus consecutive MCUs in scan order (the last may be ragged);
+ * seg_capacity < nseg is T3D_ERR_ARG.  segs == NULL fills info only, nseg included.  seg_mcus >= 1.
+ * An MCU is one 8x8 block per component (gray, 4:4:4) or 4 Y + Cb + Cr blocks = 16x16 pixels (4:2:0). */
+enum { T3D_JPEG_GRAY = 0, T3D_JPEG_444 = 1, T3D_JPEG_420 = 2 };
+enum { T3D_JPEG_REASON_NONE = 0,
+       T3D_JPEG_REASON_SOF = 1,          /* progressive, extended, lossless or arithmetic-coded frame */
+       T3D_JPEG_REASON_PRECISION = 2,    /* sample precision other than 8 bit */
+       T3D_JPEG_REASON_RESTART = 3,      /* DRI with a non-zero interval */
+       T3D_JPEG_REASON_SAMPLING = 4,     /* 4:2:2, 4:4:0 or any other sampling */
+       T3D_JPEG_REASON_COMPONENTS = 5,   /* 2, 4 or more components */
+       T3D_JPEG_REASON_SCANS = 6,        /* more than one scan */
+       T3D_JPEG_REASON_QUANT16 = 7,      /* a 16-bit quantisation table */
+       T3D_JPEG_REASON_COLOURSPACE = 8   /* three components that are not YCbCr (Adobe transform 0, ids 'R' 'G' 'B') */ };
+typedef struct {
+  int h, w, ncomp, sampling;             /* T3D_JPEG_GRAY / _444 / _420 */
+  int mcus_x, mcus_y;                    /* the MCU grid */
+  int seg_mcus, nseg;                    /* nseg = ceil(mcus_x * mcus_y / seg_mcus) */
+  long long scan_offset, scan_bytes;     /* the entropy-coded bytes (stuffed) within the file, up to the marker behind them */
+  int reason, reserved;                  /* T3D_JPEG_REASON_* when the call returned T3D_ERR_UNSUPPORTED */
+  unsigned char comp_dc[4], comp_ac[4];  /* component -> index into dc_* / ac_* */
+  unsigned char quant[3][64];            /* per component, natural (row-major) order */
+  unsigned char dc_bits[2][16], dc_vals[2][16];     /* DHT: codes per length 1..16, then the symbols in code order */
+  unsigned char ac_bits[2][16], ac_vals[2][256];
+} t3d_jpeg_info;                         /* 864 bytes */
+typedef struct {
+  unsigned int byte;                     /* the MCU's first bit lies in this byte of the stuffed scan (offset from scan_offset; */
+  short pred[3];                         /*   never a stuffed 00) ...   the DC predictor of each component at that point        */
+  unsigned char bit, reserved;           /* ... at this bit, 0 = the most significant                                           */
+  int mcu;                               /* index of the segment's first MCU (= segment index * seg_mcus)                       */
+} t3d_jpeg_seg;                          /* 16 bytes */
+int t3d_jpeg_index(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info, t3d_jpeg_seg* segs,
+                   long long seg_capacity);
+
+/* t3d_jpeg_decode_u8: B indexed files -> packed RGB uint8 [h][w][3] per image (what collate_frames packs), FIVE enqueues on
+ * `stream` whatever B is (memsets of the coefficients and of status, then the entropy, IDCT and colour kernels); no allocation, no host
+ * synchronisation, no read-back.  All tables in DEVICE memory:
+ *   data [data_bytes]      the files' bytes, image i at items[i].file_offset, file_bytes long
+ *   infos [B], segs [total_segs] (image i's nseg entries from items[i].seg_offset on), items [B]
+ *   out [out_bytes]        image i at items[i].out_offset (64 bit, any alignment: dword stores where the address allows)
+ *   work [work_bytes]      t3d_jpeg_decode_work_bytes(total_blocks) bytes, 16-byte aligned: int16 [total_blocks][64] quantised
+ *                          coefficients, then uint8 [total_blocks][64] samples; image i owns the blocks from items[i].block_offset
+ *                          on, mcus_x * mcus_y * (1, 3 or 6) of them
+ *   status int32 [B]       0: decoded to the last MCU; 1: a lane met a code that does not exist and left the rest of its
+ *                          segment's blocks zero; 2: the record is inconsistent (an info the indexer would not write, a range
+ *                          outside data / segs / out / work) -- nothing of that image is read or written
+ *   max_segs, max_blocks   upper bounds of one image's nseg and block count: they size the grids; the kernels loop, so a bound
+ *                          that is too small costs time, not correctness
+ * Memory safety does not depend on the stream: every read of it is clamped to the image's scan, at a marker or the scan's
+ * end the reader feeds zero bits and does not advance, a lane decodes at most seg_mcus MCUs of at most 64 coefficients a
+ * block and writes only its own segment's blocks.
+ * T3D_ERR_ARG, nothing launched: a NULL pointer, B < 0 or > 65535, negative or zero totals, work misaligned or work_bytes below
+ * the query, out_bytes <= 0.  B == 0 returns T3D_OK and launches nothing. */
+typedef struct {
+  long long file_offset, file_bytes;     /* within data */
+  long long out_offset;                  /* within out */
+  long long block_offset;                /* within work, in 8x8 blocks */
+  long long seg_offset;                  /* within segs */
+  long long reserved;
+} t3d_jpeg_item;                         /* 48 bytes */
+int t3d_jpeg_decode_work_bytes(long long total_blocks, long long* bytes);
+int t3d_jpeg_decode_u8(const unsigned char* data, long long data_bytes, const t3d_jpeg_info* infos, const t3d_jpeg_seg* segs,
+                       long long total_segs, const t3d_jpeg_item* items, unsigned char* out, long long out_bytes, void* work,
+                       long long work_bytes, long long total_blocks, int* status, int B, int max_segs, int max_blocks,
+                       void* stream);
+
 /* Materialise a block output:  z = act(scale*y + shift) + residual   (residual may be NULL; scale NULL = identity).
  * Replaces the BatchNorm normalise pass + `x + self.conv(x)` (mobilenetv3.py:159,162-164). y,z,residual [M,C]. */
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
