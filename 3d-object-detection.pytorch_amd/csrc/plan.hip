@@ -21,6 +21,7 @@
 #include <utility>
 #include <vector>
 
+#include "abi_entries.h"
 #include "common.h"
 
 namespace {
@@ -60,31 +61,13 @@ struct Thunk<Fn> {
 };
 
 struct Entry { const char* name; int (*run)(const uint64_t*); int nargs; };
-#define T3D_E(fn) {#fn, &Thunk<&fn>::run, arity(&fn)}
-// every entry point a step can contain (queries that return sizes / flags are not enqueue calls and are not listed)
-const Entry kEntries[] = {
-    T3D_E(t3d_dwconv_fwd), T3D_E(t3d_bn_finalize), T3D_E(t3d_bn_eval_affine), T3D_E(t3d_bn_eval_affine_batched),
-    T3D_E(t3d_pwconv_fwd), T3D_E(t3d_pwconv_dgrad), T3D_E(t3d_pack_weight),
-    T3D_E(t3d_set_dw_slots), T3D_E(t3d_set_exact_pool), T3D_E(t3d_sum_slots_batched), T3D_E(t3d_dwconv_bwd),
-    T3D_E(t3d_pwconv_wgrad), T3D_E(t3d_pwconv_yfree_prep), T3D_E(t3d_pwconv_dgrad_yfree), T3D_E(t3d_pwconv_wgrad_yfree),
-    T3D_E(t3d_pwconv_yfree_prep2), T3D_E(t3d_pwconv_bwd_yfree), T3D_E(t3d_pwconv_bwd_yfree_w), T3D_E(t3d_pwconv_wgrad_yfree_finish),
-    T3D_E(t3d_bn_bwd_finalize), T3D_E(t3d_stem_im2col), T3D_E(t3d_stem_im2col_u8), T3D_E(t3d_crop_resize_u8),
-    T3D_E(t3d_pwconv_fwd_mat), T3D_E(t3d_im2col), T3D_E(t3d_im2col_nchw), T3D_E(t3d_col2im_bwd), T3D_E(t3d_pack_conv_weight),
-    T3D_E(t3d_unpack_conv_grad), T3D_E(t3d_maxpool_fwd), T3D_E(t3d_maxpool_bwd), T3D_E(t3d_res_relu_fwd),
-    T3D_E(t3d_res_relu_bwd), T3D_E(t3d_subsample), T3D_E(t3d_ir_block_eval), T3D_E(t3d_bn_apply), T3D_E(t3d_bn_act_bwd),
-    T3D_E(t3d_gap_fwd), T3D_E(t3d_pool_fwd), T3D_E(t3d_pool_bwd), T3D_E(t3d_head_fwd),
-    T3D_E(t3d_linear_fwd), T3D_E(t3d_head_fwd_all), T3D_E(t3d_head_bwd), T3D_E(t3d_head_bwd_weights),
-    T3D_E(t3d_se_fwd_fused), T3D_E(t3d_se_bwd_data), T3D_E(t3d_se_bwd_weights), T3D_E(t3d_se_after_sums),
-    T3D_E(t3d_se_after_apply), T3D_E(t3d_se_after_bwd), T3D_E(t3d_set_reduction_replicas), T3D_E(t3d_set_workspace), T3D_E(t3d_set_main_workspace),
-    T3D_E(t3d_fold_request), T3D_E(t3d_pack_weights_batched), T3D_E(t3d_pwconv_pack_frag), T3D_E(t3d_adamw_step), T3D_E(t3d_set_grad_watch),
-    T3D_E(t3d_sgd_step), T3D_E(t3d_rmsprop_step), T3D_E(t3d_adadelta_step),
-    T3D_E(t3d_zero_batched), T3D_E(t3d_copy_cols), T3D_E(t3d_bn_bias_grad), T3D_E(t3d_se_bwd_affine), T3D_E(t3d_dropout_mask),
-    T3D_E(t3d_loss_fwd_bwd), T3D_E(t3d_metrics_per_sample), T3D_E(t3d_iou3d), T3D_E(t3d_box_iou3d), T3D_E(t3d_ssd_decode_nms),
-    T3D_E(t3d_expdw_fwd), T3D_E(t3d_track_step), T3D_E(t3d_ssd_select_rects), T3D_E(t3d_head_select), T3D_E(t3d_track_kp_to_frame),
-    T3D_E(t3d_objectron_pairs), T3D_E(t3d_objectron_hitmiss), T3D_E(t3d_draw_overlays_u8), T3D_E(t3d_ssd_multibox_loss),
-    T3D_E(t3d_ssd_head_bwd), T3D_E(t3d_ssd_cap_per_image), T3D_E(t3d_coco_match),
-};
+#define T3D_E(fn) {#fn, &Thunk<&fn>::run, arity(&fn)},
+#define T3D_NOT_IN_A_STEP(fn)
+// every entry point a step can contain: the S group of csrc/abi_entries.h (queries that return sizes / flags are not enqueue
+// calls and are in its other group)
+const Entry kEntries[] = {T3D_ABI_ENTRIES(T3D_E, T3D_NOT_IN_A_STEP)};
 #undef T3D_E
+#undef T3D_NOT_IN_A_STEP
 constexpr int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));
 constexpr int kMaxArgs = 32;       // (t3d_ssd_multibox_loss takes 29)
 

@@ -53,148 +53,59 @@ _PP = ctypes.POINTER(Prologue)
 _BP = ctypes.POINTER(BnBwd)
 _LP = ctypes.POINTER(LossCfg)
 
-# name -> argtypes (restype is always int); mirrors include/t3d.h one to one
-SIGNATURES = {
-    't3d_version': [],
-    't3d_dwconv_fwd': [_I, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_bn_finalize': [_P, _I, _D, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P],
-    't3d_bn_eval_affine': [_I, _P, _P, _P, _P, _F, _P, _P, _P],
-    't3d_bn_eval_affine_batched': [_P, _I, _F, _P],
-    't3d_pwconv_fwd': [_I, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    't3d_pwconv_dgrad': [_I, _P, _P, _BP, _P, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    't3d_pack_weight': [_I, _P, _P, _I, _I, _I, _P],
-    't3d_set_dw_slots': [_I, _P],
-    't3d_set_exact_pool': [_I],
-    't3d_set_launch_events': [_P, _P],
-    't3d_sum_slots_batched': [_P, _I, _P],
-    't3d_dwconv_bwd': [_I, _P, _P, _BP, _P, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_dwconv_route': [_I] * 10,
-    't3d_dwconv_force_route': [_I],
-    't3d_pwconv_wgrad': [_I, _P, _P, _BP, _P, _PP, _P, _I, _I, _I, _I, _P],
-    't3d_pwconv_route': [_I] * 15,
-    't3d_pwconv_force_route': [_I],
-    't3d_pwconv_yfree_prep': [_P, _BP, _P, _P, _I, _I, _P],
-    't3d_pwconv_dgrad_yfree': [_P, _P, _P, _P, _P, _PP, _P, _P, _P, _I, _I, _I, _I, _P],
-    't3d_pwconv_wgrad_yfree': [_P, _P, _BP, _P, _P, _I, _I, _I, _I, _P],
-    't3d_pwconv_yfree_prep2': [_P, _BP, _P, _P, _P, _I, _I, _P],
-    't3d_pwconv_bwd_yfree_scratch': [_I, _I, _I],
-    't3d_pwconv_bwd_yfree': [_P, _P, _P, _P, _PP, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
-    't3d_pwconv_bwd_yfree_w': [_P, _P, _P, _BP, _P, _PP, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
-    't3d_pwconv_wgrad_yfree_finish': [_P, _BP, _P, _P, _I, _I, _I, _P],
-    't3d_bn_bwd_finalize': [_P, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    't3d_stem_im2col': [_I, _P, _P, _I, _I, _I, _P],
-    't3d_stem_im2col_u8': [_I, _P, _P, _P, _P, _I, _I, _I, _P],
-    't3d_crop_resize_u8': [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    't3d_augment_crops_u8': [_P, _L, _P, _P, _I, _I, _I, _P],
-    't3d_augment_resized_u8': [_P, _L, _P, _P, _I, _I, _I, _P],
-    't3d_augment_chain_crops_u8': [_P, _L, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P],
-    't3d_augment_chain_resized_u8': [_P, _L, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P],
-    't3d_detect_augment_u8': [_P, _L, _P, _P, _I, _I, _I, _P],
-    't3d_jpeg_index': [_P, _L, _I, _P, _P, _L],
-    't3d_jpeg_decode_work_bytes': [_L, ctypes.POINTER(_L)],
-    't3d_jpeg_decode_u8': [_P, _L, _P, _P, _L, _P, _P, _L, _P, _L, _L, _P, _I, _I, _I, _P],
-    't3d_pwconv_fwd_mat': [_I, _P, _PP, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    't3d_ssd_decode_nms': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P],
-    't3d_ssd_multibox_work_bytes': [_I, _I],
-    't3d_ssd_multibox_loss': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _F, _P, _P, _L,
-                              _P, _P, _P, _P, _P, _P],
-    't3d_ssd_head_bwd_work_bytes': [_I, _P, _P, _P],
-    't3d_ssd_head_bwd': [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _P],
-    't3d_track_state_bytes': [_I],
-    't3d_track_lds_bytes': [_I, _I],
-    't3d_track_step': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _I, _D, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P],
-    't3d_ssd_select_rects': [_P, _P, _I, _I, _I, _I, _F, _F, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P],
-    't3d_head_select': [_P, _P, _I, _I, _I, _P, _P, _P],
-    't3d_track_kp_to_frame': [_P, _P, _P, _P, _I, _I, _P],
-    't3d_draw_overlays_u8': [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.POINTER(DrawStyleC), _P],
-    't3d_draw_glyphs': [_P, _I],
-    't3d_objectron_pairs': [_P] * 7 + [_I, _I, _I, _D, _D, _P, _P, _P],
-    't3d_objectron_hitmiss': [_P] * 8 + [_I] * 5 + [_P] * 6,
-    't3d_ssd_cap_per_image': [_P, _P, _I, _I, _I, _I, _P, _P],
-    't3d_coco_match': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I] + [_P] * 7,
-    't3d_im2col': [_I, _P, _PP, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    't3d_im2col_nchw': [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    't3d_col2im_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    't3d_pack_conv_weight': [_I, _P, _P, _I, _I, _I, _I, _P],
-    't3d_unpack_conv_grad': [_P, _P, _I, _I, _I, _I, _P],
-    't3d_maxpool_fwd': [_I, _P, _PP, _P, _P, _I, _I, _I, _I, _P],
-    't3d_maxpool_bwd': [_I, _P, _P, _P, _PP, _P, _P, _I, _I, _I, _I, _P],
-    't3d_res_relu_fwd': [_I, _P, _PP, _P, _PP, _P, _I, _I, _P],
-    't3d_res_relu_bwd': [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    't3d_subsample': [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_ir_block_eval': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_bn_apply': [_I, _P, _PP, _P, _P, _I, _I, _P],
-    't3d_bn_act_bwd': [_I, _P, _P, _PP, _P, _P, _I, _I, _P],
-    't3d_gap_fwd': [_I, _P, _PP, _P, _I, _I, _I, _P],
-    't3d_pool_fwd': [_I, _P, _PP, _I, _P, _P, _I, _I, _I, _P],
-    't3d_pool_bwd': [_I, _P, _P, _PP, _I, _P, _P, _P, _I, _I, _I, _P],
-    't3d_head_fwd': [_P, _PP, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    't3d_linear_fwd': [_P, _P, _P, _P, _I, _I, _I, _P],
-    't3d_head_fwd_all': [_P, _PP, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    't3d_head_bwd': [_P, _PP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    't3d_head_bwd_weights': [_P, _PP] + [_P] * 8 + [_I, _I, _I, _P],
-    't3d_se_fwd_fused': [_P] * 11 + [_I] * 4 + [_P],
-    't3d_se_bwd_data': [_P] * 13 + [_I] * 4 + [_P],
-    't3d_se_bwd_weights': [_P] * 8 + [_I] * 3 + [_P],
-    't3d_se_after_sums': [_I, _P, _P, _PP, _P, _I, _I, _I, _P],
-    't3d_se_after_apply': [_I, _P, _P, _PP, _P, _P, _P, _P, _I, _I, _I, _P],
-    't3d_se_after_bwd': [_I, _P, _P, _PP] + [_P] * 10 + [_I] * 4 + [_P],
-    't3d_set_reduction_replicas': [_I, _L],
-    't3d_set_workspace': [_P, _L],
-    't3d_set_main_workspace': [_P, _L],
-    't3d_fold_request': [_P, _P],
-    't3d_fold_pending': [],
-    't3d_pack_weights_batched': [_I, _P, _I, _P],
-    't3d_pwconv_pack_frag': [_P, _P, _I, _I, _P],
-    't3d_pwconv_frag_bytes': [_I, _I],
-    't3d_pwconv_wants_frag': [_I, _I],
-    't3d_iou3d': [_P, _P, _I, _I, _P, _P, _P, _P, _P],
-    't3d_box_iou3d': [_P, _I, _P, _P, _P],
-    't3d_adamw_step': [_P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _L, _D, _P],
-    't3d_sgd_step': [_P, _P, _P, _L, _D, _D, _D, _I, _L, _D, _P],
-    't3d_rmsprop_step': [_P, _P, _P, _L, _D, _D, _D, _D, _L, _D, _P],
-    't3d_adadelta_step': [_P, _P, _P, _P, _L, _D, _D, _D, _D, _L, _D, _P],
-    't3d_set_grad_watch': [_P],
-    't3d_zero_batched': [_P, _I, _P],
-    't3d_copy_cols': [_P, _P, _I, _I, _I, _P],
-    't3d_bn_bias_grad': [_P, _P, _I, _D, _P, _P, _P, _P, _P],
-    't3d_se_bwd_affine': [_P, _P, _P, _P, _P, _P, _I, _I, _P],
-    't3d_dropout_mask': [_P, _L, ctypes.c_ulonglong, ctypes.c_ulonglong, _F, _P],
-    't3d_loss_fwd_bwd': [_LP, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    't3d_metrics_per_sample': [_P, _P, _P, _P, _P, _I, _I, _P],
-    't3d_expdw_fwd': [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    't3d_expdw_supported': [_I, _I, _I, _I, _I, _I, _I, _I],
-    # step plans (csrc/plan.hip): record once, replay with one call
-    't3d_plan_create': [ctypes.POINTER(_P)],
-    't3d_plan_destroy': [_P],
-    't3d_plan_add_call': [_P, ctypes.c_char_p, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(_I)],
-    't3d_plan_add_fork': [_P, _P, _P],
-    't3d_plan_add_fork_after': [_P, _I, _P, _P],
-    't3d_launch_count': [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(_P)],
-    't3d_plan_add_copy_d2h': [_P, _I, _P, _L, _P],
-    't3d_plan_add_event_record': [_P, _I, _P],
-    't3d_plan_end_segment': [_P],
-    't3d_plan_num_ops': [_P, _I],
-    't3d_plan_time_entry': [_P, ctypes.c_char_p, _I],
-    't3d_plan_failed_op': [_P, ctypes.POINTER(_I)],
-    't3d_plan_run': [_P, _I, ctypes.POINTER(ctypes.c_ulonglong), _I, ctypes.POINTER(_P), _I],
-}
+# One character of the library's own description of an entry point (include/t3d.h: t3d_abi_entry) -> the ctypes type of that
+# argument.  The library makes the string from the declared function type, so nothing here repeats a signature.
+_ARGTYPE = {'i': _I, 'l': _L, 'u': ctypes.c_ulonglong, 'f': _F, 'd': _D, 'p': _P,
+            'P': _PP, 'B': _BP, 'L': _LP, 'S': ctypes.POINTER(DrawStyleC),
+            'F': _P}            # a t3d_bn_fold descriptor lives in DEVICE memory: callers pass its address, never a BnFold
+
+
+def _rows(fn, *outs):
+    """Every row of one of the library's two tables (t3d_abi_entry, t3d_abi_struct; the only signatures written by hand):
+    the values of the out-parameters `outs` per index, up to the first index the library refuses."""
+    if fn.argtypes is None:             # (once the binding is up, the table has typed these two like every other entry)
+        fn.argtypes, fn.restype = [_I] + [ctypes.POINTER(type(o)) for o in outs], _I
+    i = 0
+    while fn(i, *[ctypes.byref(o) for o in outs]) == 0:
+        yield tuple(o.value.decode() if isinstance(o, ctypes.c_char_p) else o.value for o in outs)
+        i += 1
+
+
+def abi_structs():
+    """{struct name: (sizeof, [(field, offset, bytes), ...])} of every struct of include/t3d.h, as the library's compiler laid
+    them out (t3d_abi_struct).  The ctypes classes above and the loaders' record dtypes are held to it by tests/test_abi.py."""
+    return {name: (size, [(f, int(o), int(b)) for f, o, b in (x.split(':') for x in fields.split(','))])
+            for name, size, fields in _rows(lib().t3d_abi_struct, ctypes.c_char_p(), _I(), ctypes.c_char_p())}
+
 
 _lib = None
 
 
 def lib():
-    global _lib
+    global _lib, SIGNATURES, STEP_ENTRIES
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f'{LIB_PATH} not found: build it with `python __graft_entry__.py` '
                                '(there is no CPU fallback for the HIP path)')
-        _lib = ctypes.CDLL(LIB_PATH)
+        loaded = ctypes.CDLL(LIB_PATH)
+        rows = list(_rows(loaded.t3d_abi_entry, ctypes.c_char_p(), ctypes.c_char_p(), _I()))
+        # name -> argtypes (restype is always int), and the names a recorded step may contain (t3d_plan_add_call takes them)
+        SIGNATURES = dict((name, [_ARGTYPE[c] for c in types]) for name, types, _ in rows)
+        STEP_ENTRIES = frozenset(name for name, _, in_step in rows if in_step)
         for name, args in SIGNATURES.items():
-            fn = getattr(_lib, name)
+            fn = getattr(loaded, name)
             fn.argtypes = args
             fn.restype = _I
+        _lib = loaded
     return _lib
+
+
+def __getattr__(name):
+    # SIGNATURES and STEP_ENTRIES are read from the library: asking for them loads it
+    if name in ('SIGNATURES', 'STEP_ENTRIES'):
+        lib()
+        return globals()[name]
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
 def ptr(t):

@@ -1148,6 +1148,27 @@ int t3d_plan_time_entry(t3d_plan* plan, const char* entry, int on);
 int t3d_plan_failed_op(const t3d_plan* plan, int* rc_out);
 int t3d_plan_run(t3d_plan* plan, int segment, const unsigned long long* slots, int nslots, void** events, int nevents);
 
+/* The library describes this header (csrc/abi.hip; no reference counterpart: the reference has no FFI to describe).  Both
+ * tables are made by the compiler from the declarations above, so a binding that reads them cannot disagree with the code it
+ * calls; torchdet3d/_native.py sets every `argtypes` from the first and tests/test_abi.py holds the Python mirrors of the
+ * structs to the second.  Pure host functions: no HIP call, no allocation, valid before any device is initialised; the
+ * strings are static and live as long as the library.  index runs from 0; T3D_ERR_ARG past the last row (a caller finds the
+ * end that way); any output pointer may be NULL.
+ * t3d_abi_entry: row `index` of the list of every `int t3d_*(...)` of this header (csrc/abi_entries.h).
+ *   name     the entry point;
+ *   types    one character per argument, from the declared function type:
+ *              i int   l long long   u unsigned long long   f float   d double   p any data pointer
+ *            and, for a pointer to one of the structs a caller passes as a struct of its own,
+ *              P t3d_prologue*   B t3d_bnbwd*   L t3d_loss_cfg*   S t3d_draw_style*   F t3d_bn_fold*
+ *            (an argument of any other type does not compile); the result is always int;
+ *   in_step  1 when a recorded step may contain the call (t3d_plan_add_call accepts it), else 0.
+ * t3d_abi_struct: row `index` of the list of every `typedef struct {...} t3d_*;` of this header.
+ *   name     the typedef;  size = sizeof;
+ *   fields   "name:offset:bytes" of every member in declaration order, joined by ',' -- offsetof and sizeof as the compiler
+ *            lays the struct out (an array member is one field of its whole extent). */
+int t3d_abi_entry(int index, const char** name, const char** types, int* in_step);
+int t3d_abi_struct(int index, const char** name, int* size, const char** fields);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,25 +85,10 @@ def drawn():
 
 
 def test_record_dtype_matches_the_header():
+    """(DET_SAMPLE_DTYPE against the compiler's layout of t3d_det_sample, member by member: tests/test_abi.py.)"""
     from torchdet3d.dataloaders.detection import DET_SAMPLE_DTYPE
     src = open(os.path.join(ROOT, 'include', 't3d.h')).read()
-    body = re.search(r'typedef struct \{([^}]*)\} t3d_det_sample;\s*/\* (\d+) bytes \*/', src)
-    assert body, 't3d_det_sample not found in include/t3d.h'
-    body, size = re.sub(r'/\*.*?\*/', '', body.group(1), flags=re.S), int(body.group(2))
-    width = {'long long': 8, 'int': 4, 'float': 4}
-    fields, off = [], 0
-    for decl in body.split(';'):
-        decl = decl.strip()
-        if not decl:
-            continue
-        t = next(k for k in width if decl.startswith(k + ' '))
-        for name in decl[len(t):].split(','):
-            m = re.fullmatch(r'\s*(\w+)(?:\[(\d+)\])?\s*', name)
-            off = (off + width[t] - 1) // width[t] * width[t]
-            fields.append((m.group(1), off, width[t] * int(m.group(2) or 1)))
-            off += fields[-1][2]
-    assert DET_SAMPLE_DTYPE.itemsize == size == 80 and off == 80
-    assert [(n, DET_SAMPLE_DTYPE.fields[n][1], DET_SAMPLE_DTYPE.fields[n][0].itemsize) for n in DET_SAMPLE_DTYPE.names] == fields
+    assert DET_SAMPLE_DTYPE.itemsize == 80
     flags = dict(re.findall(r'(T3D_DET_\w+) = (\d+)', src))
     from torchdet3d.dataloaders import detection as M
     assert {k: int(v) for k, v in flags.items()} == dict(

@@ -1,37 +1,9 @@
-"""CPU checks of the joined frame pipeline (torchdet3d/utils/pipeline.py, csrc/pipeline.hip): the three joint kernels are
-declared, bound and recordable into a plan, `FramePipeline` is part of the public surface and refuses to run without a
-GPU, and `SSD300.merge_classes` is the merge `SSD300.detect` used to do inline."""
-import ctypes
-
+"""CPU checks of the joined frame pipeline (torchdet3d/utils/pipeline.py, csrc/pipeline.hip): `FramePipeline` is part of the
+public surface and refuses to run without a GPU, and `SSD300.merge_classes` is the merge `SSD300.detect` used to do inline.
+(That the three joint kernels and t3d_track_step are declared, bound and recordable into a plan: tests/test_abi.py.)"""
 import numpy as np
 import pytest
 import torch
-
-JOINTS = ('t3d_ssd_select_rects', 't3d_head_select', 't3d_track_kp_to_frame')
-
-
-def test_the_three_joint_entry_points_are_bound():
-    from torchdet3d import _native as N
-    for name in JOINTS:
-        assert name in N.SIGNATURES
-        assert hasattr(N.lib(), name)
-
-
-@pytest.mark.parametrize('name', JOINTS + ('t3d_track_step',))
-def test_a_plan_accepts_the_frame_chains_entry_points(name):
-    """`t3d_plan_add_call` knows the entry point (0) and its arity (one argument fewer is an argument error, not
-    'unsupported')."""
-    from torchdet3d import _native as N
-    plan = ctypes.c_void_p()
-    assert N.lib().t3d_plan_create(ctypes.byref(plan)) == 0
-    try:
-        n = len(N.SIGNATURES[name])
-        kinds, words, sizes = (ctypes.c_int * n)(), (ctypes.c_ulonglong * n)(), (ctypes.c_int * n)()
-        assert N.lib().t3d_plan_add_call(plan, name.encode(), n, kinds, words, sizes) == 0
-        assert N.lib().t3d_plan_add_call(plan, name.encode(), n - 1, kinds, words, sizes) == -1      # T3D_ERR_ARG
-        assert N.lib().t3d_plan_num_ops(plan, 0) == 1
-    finally:
-        N.lib().t3d_plan_destroy(plan)
 
 
 def test_frame_pipeline_is_exported_and_needs_a_gpu():

@@ -97,20 +97,12 @@ def test_checkpoint_form_is_torchs_both_ways(name, torch_cls, kw):
     assert torch.equal(pt, p2)
 
 
-def test_abi_table_plan_table_and_header_name_the_three_entry_points():
-    from torchdet3d import _native as N
+def test_lr_and_step_sit_where_the_optimizers_bind_the_plan_slots():
+    """(That the three entry points are declared, typed as declared and recordable: tests/test_abi.py.)"""
     hdr = open(os.path.join(ROOT, 'include', 't3d.h')).read()
-    plan = open(os.path.join(ROOT, '3d-object-detection.pytorch_amd', 'csrc', 'plan.hip')).read()
     for n in ('t3d_sgd_step', 't3d_rmsprop_step', 't3d_adadelta_step'):
-        assert n in N.SIGNATURES and f'T3D_E({n})' in plan
         decl = re.search(r'\bint\s+%s\s*\(([^;]*)\)\s*;' % n, hdr).group(1)
-        args = [a.strip() for a in decl.split(',')]
-        assert len(args) == len(N.SIGNATURES[n])
-        for a, t in zip(args, N.SIGNATURES[n]):
-            want = N._P if '*' in a else N._D if a.startswith('double') else N._L if a.startswith('long long') else N._I
-            assert t is want, (n, a)
-        # `lr` and `step` sit where the optimizer classes bind the plan's slots
-        names = [a.split()[-1].lstrip('*') for a in args]
+        names = [a.split()[-1].lstrip('*') for a in decl.split(',')]
         src = open(os.path.join(ROOT, '3d-object-detection.pytorch_amd', 'torchdet3d', 'builders', 'optim_builder.py')).read()
         m = re.search(r"N\.call\('%s'.*?slots=\{(\d+): N\.SLOT_LR, (\d+): N\.SLOT_STEP\}" % n, src, flags=re.S)
         assert names[int(m.group(1))] == 'lr' and names[int(m.group(2))] == 'step', (n, names)

@@ -1,13 +1,12 @@
 """CPU checks of the Objectron evaluation protocol: known answers of the plain-loop restatement
 (tests/objectron_eval_ref.py), the host arithmetic of `ObjectronEvaluator.finalize` against it, the report text against a
-golden file, and the two entry points' place in the C ABI.
+golden file, and the two entry points' argument checks (their place in the C ABI: tests/test_abi.py).
 
 A note on "every AP = 1" for prediction == ground truth: the lift is an eigenvector computation, so the exact prediction's
 azimuth / polar / ADD / ADD-S come out as ~1e-10, not 0, and its IoU as 1 +- 1e-9.  At the one threshold per metric that EQUALS
 the ideal value (0 for those four, 1.0 for IoU) the comparison is decided by that rounding, in any implementation; there the
 test asks for the metric within 1e-6 of the ideal and an AP inside [0, 1].  Everywhere else -- 121 of 126 cells, the pixel
 error's threshold 0 included, where the error is exactly 0 -- AP = 1 is asserted as it stands."""
-import ctypes
 import os
 
 import numpy as np
@@ -17,9 +16,6 @@ import torch
 import objectron_eval_ref as R
 from torchdet3d.evaluation import ObjectronEvaluator
 from torchdet3d.evaluation import objectron_eval as E
-
-ENTRY_POINTS = ('t3d_objectron_pairs', 't3d_objectron_hitmiss')
-
 
 def test_constants_and_thresholds_are_the_protocols():
     assert E.METRICS == R.METRICS
@@ -119,21 +115,6 @@ def test_report_text_equals_the_golden(golden_dir, tmp_path):
     text = E.format_report(E.finalize_record(valid, n, hit, miss, sums))
     want = open(os.path.join(golden_dir, 'objectron_report.txt')).read()
     assert text == want
-
-
-def test_entry_points_are_bound_and_recordable():
-    from torchdet3d import _native as N
-    for name in ENTRY_POINTS:
-        assert name in N.SIGNATURES and hasattr(N.lib(), name)
-        plan = ctypes.c_void_p()
-        assert N.lib().t3d_plan_create(ctypes.byref(plan)) == 0
-        try:
-            k = len(N.SIGNATURES[name])
-            kinds, words, sizes = (ctypes.c_int * k)(), (ctypes.c_ulonglong * k)(), (ctypes.c_int * k)()
-            assert N.lib().t3d_plan_add_call(plan, name.encode(), k, kinds, words, sizes) == 0
-            assert N.lib().t3d_plan_add_call(plan, name.encode(), k - 1, kinds, words, sizes) == -1      # T3D_ERR_ARG
-        finally:
-            N.lib().t3d_plan_destroy(plan)
 
 
 def test_null_and_out_of_range_arguments_are_refused_before_any_launch():

@@ -1,15 +1,12 @@
 """CPU checks of the SSD heads' training step: the restatement (tests/ssd_head_ref.py) against torch.nn modules, the learning
-rate schedule, the C-ABI symbol, and the flat parameter layout of SSD300 (no device work)."""
+rate schedule, and the flat parameter layout of SSD300 (no device work; the C-ABI symbols: tests/test_abi.py)."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import ssd_head_ref as R
-from conftest import ROOT
 
 
 def _hand_head(seed=0, B=2, H=5, W=4, C=8, n=6):
@@ -121,18 +118,6 @@ def test_sgd_restatement_against_torch_optim():
         opt.step()
         q, buf = R.sgd_step(q, gr.numpy(), buf, 0.05)
         assert np.abs(q - p.detach().numpy()).max() < 1e-14
-
-
-def test_symbol_is_declared_bound_and_in_the_plan_table():
-    from torchdet3d import _native as N
-    hdr = open(os.path.join(ROOT, 'include', 't3d.h')).read()
-    plan = open(os.path.join(ROOT, '3d-object-detection.pytorch_amd', 'csrc', 'plan.hip')).read()
-    for name in ('t3d_ssd_head_bwd', 't3d_ssd_head_bwd_work_bytes'):
-        assert re.search(r'\bint\s+' + name + r'\s*\(', hdr), name
-        assert name in N.SIGNATURES
-    decl = re.search(r'int\s+t3d_ssd_head_bwd\s*\(([^;]*)\)\s*;', hdr).group(1)
-    assert len(decl.split(',')) == len(N.SIGNATURES['t3d_ssd_head_bwd'])
-    assert 'T3D_E(t3d_ssd_head_bwd)' in plan and 'T3D_E(t3d_ssd_head_bwd_work_bytes)' not in plan
 
 
 def test_flat_layout():

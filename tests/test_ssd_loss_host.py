@@ -147,22 +147,3 @@ def test_bad_arguments_are_refused_on_the_host():
     assert call(beta=0.0) == N.ERR_ARG and call(ratio=-1) == N.ERR_ARG
     assert call(neg=0.3) == N.ERR_UNSUPPORTED                 # an ignore band is not built
     assert call(G=65) == N.ERR_UNSUPPORTED and call(hw=I(8193)) == N.ERR_UNSUPPORTED      # past the LDS plan: A <= 16384, G <= 64
-
-
-def test_a_plan_accepts_the_entry_point():
-    """`t3d_plan_add_call` knows t3d_ssd_multibox_loss and its 29 arguments, so a later detector step can record it; the size
-    query is not an enqueue call and is not in the table."""
-    from torchdet3d import _native as N
-    name = 't3d_ssd_multibox_loss'
-    plan = ctypes.c_void_p()
-    assert N.lib().t3d_plan_create(ctypes.byref(plan)) == 0
-    try:
-        n = len(N.SIGNATURES[name])
-        assert n == 29
-        kinds, words, sizes = (ctypes.c_int * n)(), (ctypes.c_ulonglong * n)(), (ctypes.c_int * n)()
-        assert N.lib().t3d_plan_add_call(plan, name.encode(), n, kinds, words, sizes) == 0
-        assert N.lib().t3d_plan_add_call(plan, name.encode(), n - 1, kinds, words, sizes) == N.ERR_ARG
-        assert N.lib().t3d_plan_add_call(plan, b't3d_ssd_multibox_work_bytes', 2, kinds, words, sizes) == N.ERR_UNSUPPORTED
-        assert N.lib().t3d_plan_num_ops(plan, 0) == 1
-    finally:
-        N.lib().t3d_plan_destroy(plan)
