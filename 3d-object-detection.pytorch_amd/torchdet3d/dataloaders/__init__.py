@@ -3,4 +3,4 @@ from .objectron import Objectron, AugmentPipeline, build_augmentations, collate_
 from .gpu_loader import GpuAugmentLoader
 from .detection import ObjectronFrames, DetectionAugmentPipeline, collate_frames
 from .gpu_detection_loader import GpuDetectionLoader
-from .jpeg import JpegIndex, decode_jpeg_batch, index_jpeg, collate_jpeg
+from .jpeg import JpegIndex, decode_jpeg_batch, index_jpeg, collate_jpeg, plan_roi, decode_jpeg_rois

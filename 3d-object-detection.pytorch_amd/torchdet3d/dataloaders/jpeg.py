@@ -11,6 +11,11 @@ frames of a batch in parallel into the packed frame buffer `t3d_detect_augment_u
 A file the device path does not take (progressive, restart markers, 4:2:2, CMYK, ... or malformed) keeps its reason in the
 index and is decoded on the host as before.
 
+The regression loader cuts one object's box out of each frame; the form for it decodes only that pixel RECTANGLE:
+`plan_roi` works out, on the host and in numpy, which MCUs the rectangle's pixels read, which segments own them and which bytes
+of the file those segments lie in; only that byte span has to be read and uploaded, and `t3d_jpeg_decode_roi_u8`
+(`launch_decode_roi`, `decode_jpeg_rois`) writes the packed crops `collate_crops` packs from host-decoded frames.
+
 `decode_jpeg_batch(files, rows)` is the one-call form: a list of file contents and their index rows -> the packed device
 buffer and its descriptor table, the layout `collate_frames` produces."""
 import os
@@ -19,7 +24,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 __all__ = ['JpegIndex', 'decode_jpeg_batch', 'index_jpeg', 'collate_jpeg', 'INFO_DTYPE', 'SEG_DTYPE', 'ITEM_DTYPE',
-           'DEFAULT_SEG_MCUS', 'REASONS']
+           'DEFAULT_SEG_MCUS', 'REASONS', 'roi_mcus', 'plan_roi', 'plan_roi_batch', 'launch_decode_roi', 'decode_jpeg_rois',
+           'ROI_SEG_MCUS', 'ROI_READ_AHEAD']
 
 # include/t3d.h: t3d_jpeg_info (864 bytes), t3d_jpeg_seg (16), t3d_jpeg_item (48)
 INFO_DTYPE = np.dtype([('h', '<i4'), ('w', '<i4'), ('ncomp', '<i4'), ('sampling', '<i4'), ('mcus_x', '<i4'), ('mcus_y', '<i4'),
@@ -37,6 +43,11 @@ REASONS = {0: 'decoded on the device', 1: 'not a baseline frame (progressive, ex
            2: 'sample precision other than 8 bit', 3: 'restart interval', 4: 'sampling other than 4:4:4 / 4:2:0',
            5: 'component count other than 1 or 3', 6: 'more than one scan', 7: '16-bit quantisation table',
            8: 'three components that are not YCbCr', -1: 'malformed'}
+# the same for an index made for the rectangle decode: tools/time_roi_decode.py sweeps 1 .. 16: the best
+# of the sweep
+ROI_SEG_MCUS = 1
+# bytes uploaded behind the byte the segment after the last needed one begins in: the device's 64-bit window reads ahead
+ROI_READ_AHEAD = 8
 _BLOCKS_PER_MCU = (1, 3, 6)             # gray, 4:4:4, 4:2:0
 _MAGIC = 0x7833644A50454731             # 'x3dJPEG1'
 
@@ -230,3 +241,147 @@ def decode_jpeg_batch(files, rows, device=None):
 
 
 decode_jpeg_batch.last_status = None
+
+
+# ---- one pixel rectangle per file: t3d_jpeg_decode_roi_u8 ---------------------------------------------------------------------
+def roi_mcus(sampling, h, w, x0, y0, x1, y1):
+    """The MCU rectangle (mx0, my0, mx1, my1) holding every block the full decode reads for the pixels [x0, x1) x [y0, y1) of an
+    h x w image (include/t3d.h next to t3d_jpeg_decode_roi_u8; csrc/jpeg_decode.h: roi_mcus).  Gray / 4:4:4: the pixels' MCUs.
+    4:2:0: fancy upsampling of pixel (y, x) also reads chroma row (y >> 1) - 1 (y even) or + 1 (y odd) and chroma column
+    (x >> 1) - 1 (x even) or + 1 (x odd), clamped to the real samples; for dw <= 2 libjpeg replicates and reads no neighbour."""
+    if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):
+        raise ValueError(f'the rectangle [{x0}, {x1}) x [{y0}, {y1}) is empty or outside the {h} x {w} image')
+    if sampling != 2:
+        return x0 >> 3, y0 >> 3, ((x1 - 1) >> 3) + 1, ((y1 - 1) >> 3) + 1
+    dh, dw = (h + 1) >> 1, (w + 1) >> 1
+    cx0, cx1, cy0, cy1 = x0 >> 1, (x1 - 1) >> 1, y0 >> 1, (y1 - 1) >> 1          # chroma samples, inclusive
+    if dw > 2:
+        if not x0 & 1:
+            cx0 = max(cx0 - 1, 0)
+        if (x1 - 1) & 1:
+            cx1 = min(cx1 + 1, dw - 1)
+        if not y0 & 1:
+            cy0 = max(cy0 - 1, 0)
+        if (y1 - 1) & 1:
+            cy1 = min(cy1 + 1, dh - 1)
+    return cx0 >> 3, cy0 >> 3, (cx1 >> 3) + 1, (cy1 >> 3) + 1
+
+
+def plan_roi(info, segs, x0, y0, x1, y1):
+    """Pure numpy: what decoding the pixels [x0, x1) x [y0, y1) of one indexed file takes.  info, segs: the file's index rows
+    (`JpegIndex.rows`; segs may be a memory map -- only two of its entries are read).  -> dict:
+      rect (x0, y0, x1, y1);  mcus (mx0, my0, mx1, my1), `roi_mcus`
+      row_segs int64 [my1 - my0, 2]: MCU row my0 + r needs the segments row_segs[r, 0] .. row_segs[r, 1] - 1; a segment that
+                 straddles rows is listed in the first row that needs it, so every needed segment appears once
+      seg_first, seg_count: the contiguous run of the file's segments from the first needed to the last needed one
+      span (first, bytes): the bytes of the SCAN (offsets from info['scan_offset']) from the first needed segment's byte to the
+                 byte of the segment behind the last needed one plus ROI_READ_AHEAD, or to the scan's end
+      blocks: 8x8 blocks of the MCU rectangle;  lanes, runs: the item's share of the call's grid bounds."""
+    h, w, S, X = int(info['h']), int(info['w']), int(info['seg_mcus']), int(info['mcus_x'])
+    x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
+    mx0, my0, mx1, my1 = roi_mcus(int(info['sampling']), h, w, x0, y0, x1, y1)
+    if my1 - my0 <= 8:                               # (a handful of rows: faster without numpy)
+        b = [(my * X + mx1 - 1) // S for my in range(my0, my1)]
+        a = [max((my * X + mx0) // S, b[r - 1] + 1 if r else 0) for r, my in enumerate(range(my0, my1))]
+        row_segs = np.array([(u, max(v + 1, u)) for u, v in zip(a, b)], np.int64)
+    else:
+        base = np.arange(my0, my1, dtype=np.int64) * X
+        a, b = (base + mx0) // S, (base + mx1 - 1) // S
+        a[1:] = np.maximum(a[1:], b[:-1] + 1)
+        row_segs = np.stack([a, np.maximum(b + 1, a)], 1)
+    s_lo, s_hi = int(a[0]), int(b[-1])
+    first = int(segs[s_lo]['byte'])
+    scan_bytes = int(info['scan_bytes'])
+    end = min(int(segs[s_hi + 1]['byte']) + ROI_READ_AHEAD, scan_bytes) if s_hi + 1 < int(info['nseg']) else scan_bytes
+    rw, rh = mx1 - mx0, my1 - my0
+    return dict(rect=(x0, y0, x1, y1), mcus=(mx0, my0, mx1, my1), row_segs=row_segs, seg_first=s_lo, seg_count=s_hi - s_lo + 1,
+                span=(first, end - first), blocks=rw * rh * _BLOCKS_PER_MCU[int(info['sampling'])],
+                lanes=rh * ((rw - 1) // S + 2), runs=(y1 - y0) * ((x1 - x0 + 3) // 4))
+
+
+def plan_roi_batch(rows, plans, data_offsets, out_offsets, spans=None):
+    """The tables of one t3d_jpeg_decode_roi_u8 call.  rows [(info, segs)] and plans [`plan_roi`] of the batch's items;
+    data_offsets: where each item's uploaded scan bytes lie in the data buffer; spans [(first, bytes)]: which bytes of the scan
+    those are (None: each plan's own span); out_offsets: where each crop goes.
+    -> dict(infos, segs, items, rects (numpy, to upload), total_segs, total_blocks, max_lanes, max_blocks, max_runs)."""
+    infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
+    for inf, (_, s) in zip(infos, rows):
+        if int(inf['reason']) or int(inf['nseg']) != len(s) or int(inf['nseg']) < 1:
+            raise ValueError('an index row of a file the device does not decode (its reason is set, or its table is incomplete)')
+    segs = np.concatenate([np.asarray(r[1][p['seg_first']:p['seg_first'] + p['seg_count']]) for r, p in zip(rows, plans)]
+                          + [np.zeros(0, SEG_DTYPE)])
+    spans = [p['span'] for p in plans] if spans is None else spans
+    nseg = np.array([p['seg_count'] for p in plans], np.int64)
+    blocks = np.array([p['blocks'] for p in plans], np.int64)
+    items = np.zeros(len(rows), ITEM_DTYPE)
+    items['file_offset'], items['out_offset'] = data_offsets, out_offsets
+    items['reserved'], items['file_bytes'] = [s[0] for s in spans], [s[1] for s in spans]
+    items['block_offset'], items['seg_offset'] = np.cumsum(blocks) - blocks, np.cumsum(nseg) - nseg
+    rects = np.zeros((len(rows), 12), np.int32)
+    for k, p in enumerate(plans):
+        rects[k, :10] = p['rect'] + p['mcus'] + (p['seg_first'], p['seg_count'])
+    return dict(infos=infos, segs=segs, items=items, rects=rects, total_segs=len(segs), total_blocks=int(blocks.sum()),
+                max_lanes=max(p['lanes'] for p in plans), max_blocks=int(blocks.max()), max_runs=max(p['runs'] for p in plans))
+
+
+def launch_decode_roi(data, infos, segs, items, rects, plan, out):
+    """Enqueue t3d_jpeg_decode_roi_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items, rects: device
+    uint8 tensors holding plan['infos'], ['segs'], ['items'], ['rects'] (`plan_roi_batch`).  -> status, device int32 [B]."""
+    import ctypes
+
+    import torch
+
+    from .. import _native as N
+    B = len(plan['infos'])
+    nbytes = ctypes.c_longlong(0)
+    if N.lib().t3d_jpeg_decode_work_bytes(plan['total_blocks'], ctypes.byref(nbytes)) != 0:
+        raise RuntimeError('t3d_jpeg_decode_work_bytes failed')
+    work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=out.device)
+    status = torch.empty(max(B, 1), dtype=torch.int32, device=out.device)
+    N.call('t3d_jpeg_decode_roi_u8', N.ptr(data), data.numel(), N.ptr(infos), N.ptr(segs), plan['total_segs'], N.ptr(items),
+           N.ptr(rects), N.ptr(out), out.numel(), N.ptr(work), work.numel(), plan['total_blocks'], N.ptr(status), B,
+           plan['max_lanes'], plan['max_blocks'], plan['max_runs'], N.stream())
+    return status[:B]
+
+
+def _upload_parts(parts, dev):
+    """numpy uint8 arrays -> their device views inside ONE uploaded buffer (each part 16-byte aligned)."""
+    import torch
+    offs = np.concatenate([[0], np.cumsum([-(-p.size // 16) * 16 for p in parts])])
+    host = np.zeros(max(int(offs[-1]), 16), np.uint8)
+    for p, o in zip(parts, offs):
+        host[o:o + p.size] = p
+    d = torch.from_numpy(host).to(dev)
+    return [d[o:o + p.size] for p, o in zip(parts, offs)]
+
+
+def decode_jpeg_rois(files, rows, rects, device=None, partial=True):
+    """files: the contents of B JPEG files; rows: their index rows; rects [B] (x0, y0, x1, y1) -> (packed device uint8
+    [sum h * w * 3], desc int64 [B, 3] = (offset, h, w)): the rectangles as RGB, the buffer and table `collate_crops` produces
+    for the sliced frames.  partial: upload each file's planned byte span only (else its whole scan).  One
+    t3d_jpeg_decode_roi_u8 call on the current stream; `decode_jpeg_rois.last_status` holds its device status vector."""
+    import torch
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    B = len(files)
+    desc = np.zeros((B, 3), np.int64)
+    for i, (x0, y0, x1, y1) in enumerate(rects):
+        desc[i, 1], desc[i, 2] = y1 - y0, x1 - x0
+    nb = desc[:, 1] * desc[:, 2] * 3
+    desc[:, 0] = np.cumsum(nb) - nb
+    out = torch.empty(max(int(nb.sum()), 1), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return out, desc
+    plans = [plan_roi(inf, sg, *r) for (inf, sg), r in zip(rows, rects)]
+    spans = [p['span'] if partial else (0, int(inf['scan_bytes'])) for p, (inf, _) in zip(plans, rows)]
+    arrs = [np.frombuffer(f, np.uint8)[int(inf['scan_offset']) + a:int(inf['scan_offset']) + a + n]
+            for f, (inf, _), (a, n) in zip(files, rows, spans)]
+    sizes = np.array([a.size for a in arrs], np.int64)
+    plan = plan_roi_batch(rows, plans, np.cumsum(sizes) - sizes, desc[:, 0], spans)
+    data, infos, segs, items, rct = _upload_parts([np.concatenate(arrs)] + [plan[k].reshape(-1).view(np.uint8) for k in
+                                                                            ('infos', 'segs', 'items', 'rects')], dev)
+    decode_jpeg_rois.last_status = launch_decode_roi(data, infos, segs, items, rct, plan, out)
+    return out, desc
+
+
+decode_jpeg_rois.last_status = None
+

@@ -494,6 +494,49 @@ int t3d_jpeg_decode_u8(const unsigned char* data, long long data_bytes, const t3
                        long long work_bytes, long long total_blocks, int* status, int B, int max_segs, int max_blocks,
                        void* stream);
 
+/* t3d_jpeg_decode_roi_u8: of each of B indexed files ONE PIXEL RECTANGLE [x0, x1) x [y0, y1) -> packed RGB uint8
+ * [y1 - y0][x1 - x0][3] at the item's out_offset: what Objectron.crop slices out of the decoded frame and collate_crops packs,
+ * so t3d_augment_crops_u8, its chain variant and the cache fill read it through the same (offset, h, w) descriptor.
+ * DEFINITION: the pixels are those t3d_jpeg_decode_u8 writes for the same file, sliced [y0:y1, x0:x1], bit for bit -- the
+ * definition above (islow IDCT, fancy 4:2:0 upsampling with its edge rules on the REAL image's dh, dw, the 16.16 colour
+ * constants) plus the slice.  Only the work differs: entropy decoding of the segments that own an MCU the rectangle reads, each
+ * once (inside such a segment the MCUs outside are parsed -- bits and DC predictors advance -- and not stored), the IDCT of the
+ * rectangle's blocks, the colour conversion of the rectangle's pixels.  The same FIVE enqueues whatever B is; no allocation, no
+ * host synchronisation, no read-back.
+ *   MCU rectangle [mx0, mx1) x [my0, my1), computed by the caller and checked here: it must hold every block the rectangle's
+ *     pixels read.  Gray, 4:4:4: the pixels' own MCUs, x >> 3, y >> 3.  4:2:0: pixel (y, x) reads chroma rows y >> 1 and
+ *     (y >> 1) - 1 (y even) / + 1 (y odd) and chroma columns x >> 1 and (x >> 1) - 1 (x even) / + 1 (x odd), clamped to
+ *     [0, dh - 1] / [0, dw - 1] -- the rectangle halved and dilated by the one sample its edge pixels reach for; chroma sample s
+ *     lies in MCU s >> 3 (which covers the luma).  dw <= 2: libjpeg replicates, no dilation.  A larger rectangle is accepted.
+ *   infos [B]              the files' t3d_jpeg_info (scan_offset is not used here: the items say where the bytes are)
+ *   items [B]              t3d_jpeg_item read this way: file_offset, file_bytes: where in `data` the item's uploaded bytes of the
+ *                          SCAN lie and how many there are; reserved: the byte of the scan (offset from scan_offset) they begin
+ *                          at -- the whole scan is (file's offset + scan_offset, scan_bytes, 0); out_offset (any alignment: a lane
+ *                          stores dwords where its own address allows, bytes otherwise); block_offset, in 8x8 blocks; seg_offset
+ *   rects int32 [B][12]    x0 y0 x1 y1  mx0 my0 mx1 my1  seg_first seg_count  0 0: segs[seg_offset + k] is the file's segment
+ *                          seg_first + k, k < seg_count; the uploaded segments must include the first and the last the MCU
+ *                          rectangle needs, those of MCU (my0, mx0) and MCU (my1 - 1, mx1 - 1)
+ *   work [work_bytes]      t3d_jpeg_decode_work_bytes(total_blocks) bytes, 16-byte aligned, total_blocks the sum over the items
+ *                          of (mx1 - mx0) * (my1 - my0) * (1, 3 or 6): COMPACT, blocks exist for the MCU rectangles only
+ *   Partial data: the reader treats every byte outside the uploaded span as the end of the scan -- it feeds zero bits and does
+ *     not advance.  The span from the byte of the first needed segment to the byte of the segment behind the last needed one,
+ *     plus 8 bytes (the window reads ahead), decodes like the whole scan.
+ *   status int32 [B]       0: decoded; 1: a lane met a code that does not exist (or its segment begins outside the uploaded
+ *                          bytes) and left the rest of its segment zero; 2: the record is inconsistent (an info the indexer would
+ *                          not write, an empty rectangle or one outside the image, an MCU rectangle outside the grid or not
+ *                          holding the blocks the pixels read, uploaded segments that miss a needed one, a range outside data /
+ *                          scan / segs / out / work) -- nothing of that item is read or written
+ *   max_lanes, max_blocks, max_runs   upper bounds over the items of (my1 - my0) * ((mx1 - mx0 - 1) / seg_mcus + 2), of the
+ *                          MCU rectangle's block count and of (y1 - y0) * ceil((x1 - x0) / 4): they size the grids; the kernels
+ *                          loop, so a bound that is too small costs time, not correctness
+ * Memory safety as above: every per-item range is checked by every kernel before use, every stream read is clamped to the
+ * uploaded bytes, a block ends at coefficient 63, a lane writes only blocks of its own segment that lie in the rectangle.
+ * T3D_ERR_ARG, nothing launched: as t3d_jpeg_decode_u8, and rects NULL or a bound below 1.  B == 0 returns T3D_OK. */
+int t3d_jpeg_decode_roi_u8(const unsigned char* data, long long data_bytes, const t3d_jpeg_info* infos, const t3d_jpeg_seg* segs,
+                           long long total_segs, const t3d_jpeg_item* items, const int* rects, unsigned char* out,
+                           long long out_bytes, void* work, long long work_bytes, long long total_blocks, int* status, int B,
+                           long long max_lanes, int max_blocks, long long max_runs, void* stream);
+
 /* Materialise a block output:  z = act(scale*y + shift) + residual   (residual may be NULL; scale NULL = identity).
  * Replaces the BatchNorm normalise pass + `x + self.conv(x)` (mobilenetv3.py:159,162-164). y,z,residual [M,C]. */
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
