@@ -15,6 +15,14 @@
 // entropy lanes are the segments that own an MCU of the rectangle's MCU rectangle, each once; coefficient and sample blocks exist
 // for that MCU rectangle only, so the memset, the IDCT and the colour pass scale with the crop; the bytes may be the part of the
 // scan those segments lie in.
+// Both entry points decode ITEMS, windows of an image (csrc/jpeg_decode.h: the whole image, or a rectangle), with the same
+// segment parser, IDCT and pixel arithmetic; here they share the argument list (JPEG_ARGS) and the argument checks
+// (check_call).  Each kernel keeps its own lines around the lane calls, the table expansion of the two entropy kernels
+// included: one body for both windows, and one function for the tables, change the kernels' code, and the whole-frame and
+// the rectangle call were measured slower with them (finding 71).  As they stand the six kernels are the
+// instructions they were before the parsers became one.  An entry point also keeps its grid -- a whole frame's from
+// segments and blocks, a rectangle's from the planner's lanes and runs -- and its two memsets, which common.h's rule wants
+// in front of its launches.
 // Memory safety is in the code, not in the stream: the reader clamps every index to the image's scan and feeds zeros behind
 // it, the block loop ends at coefficient 63, a lane stays inside its segment's blocks, and every per-image range is checked
 // against the buffers before anything of that image is touched (status 2).
@@ -31,22 +39,27 @@ namespace {
 namespace L = t3d_jpeg_lane;
 static_assert(sizeof(t3d_jpeg_info) == 864 && sizeof(t3d_jpeg_seg) == 16 && sizeof(t3d_jpeg_item) == 48, "include/t3d.h");
 
-#define JPEG_ARGS                                                                                                              \
+// the buffers of a call, in the ABI's order; the rectangle kernels put `const int *__restrict__ rects,` into the slot behind items
+#define JPEG_ARGS(...)                                                                                                         \
   const unsigned char *__restrict__ data, long long data_bytes, const t3d_jpeg_info *__restrict__ infos,                       \
-      const t3d_jpeg_seg *__restrict__ segs, long long total_segs, const t3d_jpeg_item *__restrict__ items, unsigned char *out, \
-      long long out_bytes, void *work, long long total_blocks
-#define JPEG_GEOM(img) L::geom(data, data_bytes, infos + (img), segs, total_segs, items[img], out, out_bytes, work, total_blocks)
+      const t3d_jpeg_seg *__restrict__ segs, long long total_segs, const t3d_jpeg_item *__restrict__ items,                    \
+      __VA_ARGS__ unsigned char *out, long long out_bytes, void *work, long long total_blocks
+#define JPEG_RECTS const int *__restrict__ rects,
+// item i of the call, checked: the whole image, or the rectangle rects[i] of it
+#define JPEG_GEOM(i) L::geom(data, data_bytes, infos + (i), segs, total_segs, items[i], out, out_bytes, work, total_blocks)
+#define JPEG_ROI(i) L::roi_geom(data, data_bytes, infos + (i), segs, total_segs, items[i], rects + 12 * (i), out, out_bytes, work, total_blocks)
 
-__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JPEG_ARGS, int* __restrict__ status) {
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JPEG_ARGS(), int* __restrict__ status) {
   __shared__ t3d_jpeg_huff tab[4];                      // DC 0, DC 1, AC 0, AC 1
   __shared__ int tab_ok[4];
   const int img = blockIdx.y;
-  const t3d_jpeg_info* info = infos + img;
-  const L::Geom g = JPEG_GEOM(img);
+  const L::Roi r = L::whole(JPEG_GEOM(img));            // (the one copy of the geometry here: a second one changes the code)
+  const L::Geom& g = r.g;
   if (!g.ok) {                                          // (uniform in the workgroup)
     if (blockIdx.x == 0 && threadIdx.x == 0) status[img] = 2;
     return;
   }
+  const t3d_jpeg_info* info = infos + img;
   if (threadIdx.x < 4) {
     const int t = threadIdx.x & 1;
     tab_ok[threadIdx.x] = threadIdx.x < 2 ? t3d_jpeg_build_huff(info->dc_bits[t], info->dc_vals[t], 16, &tab[threadIdx.x])
@@ -66,10 +79,10 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(JPEG_ARGS, int* __rest
     return;
   }
   for (int s = blockIdx.x * 64 + threadIdx.x; s < g.nseg; s += gridDim.x * 64)
-    if (!L::decode_segment(g, tab, dci, aci, s)) status[img] = 1;
+    if (!L::decode_segment<false>(r, tab, dci, aci, s)) status[img] = 1;
 }
 
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(JPEG_ARGS) {
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(JPEG_ARGS()) {
   __shared__ int quant[3 * 64];
   const int img = blockIdx.y;
   const L::Geom g = JPEG_GEOM(img);
@@ -79,7 +92,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(JPEG_ARGS) {
   for (long long blk = blockIdx.x * 256ll + threadIdx.x; blk < g.nblocks; blk += gridDim.x * 256ll) L::idct_block(g, quant, blk);
 }
 
-__global__ __launch_bounds__(256) void jpeg_colour_kernel(JPEG_ARGS) {
+__global__ __launch_bounds__(256) void jpeg_colour_kernel(JPEG_ARGS()) {
   const L::Geom g = JPEG_GEOM(blockIdx.y);
   if (!g.ok) return;
   const long long nrun = ((long long)g.h * g.w + 3) / 4;
@@ -87,25 +100,19 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(JPEG_ARGS) {
   for (long long t = blockIdx.x * 256ll + threadIdx.x; t < nrun; t += gridDim.x * 256ll) L::colour_run(g, t, aligned);
 }
 
-// ---- a pixel rectangle per item ---------------------------------------------------------------------------------------------
-#define JPEG_ROI_ARGS                                                                                                          \
-  const unsigned char *__restrict__ data, long long data_bytes, const t3d_jpeg_info *__restrict__ infos,                       \
-      const t3d_jpeg_seg *__restrict__ segs, long long total_segs, const t3d_jpeg_item *__restrict__ items,                    \
-      const int *__restrict__ rects, unsigned char *out, long long out_bytes, void *work, long long total_blocks
-#define JPEG_ROI(i) L::roi_geom(data, data_bytes, infos + (i), segs, total_segs, items[i], rects + 12 * (i), out, out_bytes, work, total_blocks)
-
-__global__ __launch_bounds__(64) void jpeg_roi_entropy_kernel(JPEG_ROI_ARGS, int* __restrict__ status) {
+// ---- a pixel rectangle per item: the grid is sized for the call's largest, so the workgroups a smaller one does not need leave first
+__global__ __launch_bounds__(64) void jpeg_roi_entropy_kernel(JPEG_ARGS(JPEG_RECTS), int* __restrict__ status) {
   __shared__ t3d_jpeg_huff tab[4];                      // DC 0, DC 1, AC 0, AC 1
   __shared__ int tab_ok[4];
   const int img = blockIdx.y;
-  const t3d_jpeg_info* info = infos + img;
   const L::Roi r = JPEG_ROI(img);
   if (!r.g.ok) {                                        // (uniform in the workgroup)
     if (blockIdx.x == 0 && threadIdx.x == 0) status[img] = 2;
     return;
   }
   const long long lanes = (long long)(r.my1 - r.my0) * r.per_row;
-  if (blockIdx.x * 64ll >= lanes) return;               // (uniform: a small rectangle in a grid sized for the largest)
+  if (blockIdx.x * 64ll >= lanes) return;               // (uniform)
+  const t3d_jpeg_info* info = infos + img;
   if (threadIdx.x < 4) {
     const int t = threadIdx.x & 1;
     tab_ok[threadIdx.x] = threadIdx.x < 2 ? t3d_jpeg_build_huff(info->dc_bits[t], info->dc_vals[t], 16, &tab[threadIdx.x])
@@ -126,11 +133,11 @@ __global__ __launch_bounds__(64) void jpeg_roi_entropy_kernel(JPEG_ROI_ARGS, int
   }
   for (long long t = blockIdx.x * 64ll + threadIdx.x; t < lanes; t += gridDim.x * 64ll) {
     const int s = L::roi_lane_segment(r, t);
-    if (s >= 0 && !L::decode_segment_roi(r, tab, dci, aci, s)) status[img] = 1;
+    if (s >= 0 && !L::decode_segment<true>(r, tab, dci, aci, s)) status[img] = 1;
   }
 }
 
-__global__ __launch_bounds__(256) void jpeg_roi_idct_kernel(JPEG_ROI_ARGS) {
+__global__ __launch_bounds__(256) void jpeg_roi_idct_kernel(JPEG_ARGS(JPEG_RECTS)) {
   __shared__ int quant[3 * 64];
   const int img = blockIdx.y;
   const L::Roi r = JPEG_ROI(img);
@@ -140,11 +147,23 @@ __global__ __launch_bounds__(256) void jpeg_roi_idct_kernel(JPEG_ROI_ARGS) {
   for (long long blk = blockIdx.x * 256ll + threadIdx.x; blk < r.g.nblocks; blk += gridDim.x * 256ll) L::idct_block(r.g, quant, blk);
 }
 
-__global__ __launch_bounds__(256) void jpeg_roi_colour_kernel(JPEG_ROI_ARGS) {
+__global__ __launch_bounds__(256) void jpeg_roi_colour_kernel(JPEG_ARGS(JPEG_RECTS)) {
   const L::Roi r = JPEG_ROI(blockIdx.y);
   if (!r.g.ok) return;
   const long long nrun = (long long)(r.y1 - r.y0) * ((r.x1 - r.x0 + 3) >> 2);
   for (long long t = blockIdx.x * 256ll + threadIdx.x; t < nrun; t += gridDim.x * 256ll) L::colour_run_roi(r, t);
+}
+
+// What both entry points check of their arguments (ptrs: every pointer is there; bounds: every grid bound is >= 1).
+// -> T3D_ERR_ARG, or T3D_OK: for B == 0 nothing else was looked at and nothing is to be done
+int check_call(int B, bool ptrs, long long data_bytes, long long total_segs, long long out_bytes, const void* work, long long work_bytes,
+               long long total_blocks, bool bounds) {
+  if (B < 0 || B > 65535) return T3D_ERR_ARG;
+  if (B == 0) return T3D_OK;
+  if (!ptrs || !bounds) return T3D_ERR_ARG;
+  if (data_bytes <= 0 || total_segs <= 0 || out_bytes <= 0 || total_blocks <= 0 || total_blocks > (1ll << 40)) return T3D_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < total_blocks * 192) return T3D_ERR_ARG;
+  return T3D_OK;
 }
 
 }  // namespace
@@ -159,12 +178,9 @@ extern "C" int t3d_jpeg_decode_u8(const unsigned char* data, long long data_byte
                                   long long total_segs, const t3d_jpeg_item* items, unsigned char* out, long long out_bytes, void* work,
                                   long long work_bytes, long long total_blocks, int* status, int B, int max_segs, int max_blocks,
                                   void* stream) {
-  if (B < 0 || B > 65535) return T3D_ERR_ARG;
-  if (B == 0) return T3D_OK;
-  if (!data || !infos || !segs || !items || !out || !work || !status) return T3D_ERR_ARG;
-  if (data_bytes <= 0 || total_segs <= 0 || out_bytes <= 0 || total_blocks <= 0 || total_blocks > (1ll << 40)) return T3D_ERR_ARG;
-  if (max_segs < 1 || max_blocks < 1) return T3D_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < total_blocks * 192) return T3D_ERR_ARG;
+  const int rc = check_call(B, data && infos && segs && items && out && work && status, data_bytes, total_segs, out_bytes, work, work_bytes,
+                            total_blocks, max_segs >= 1 && max_blocks >= 1);
+  if (rc != T3D_OK || B == 0) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(work, 0, (size_t)total_blocks * 128, st) != hipSuccess) return T3D_ERR_LAUNCH;
   if (hipMemsetAsync(status, 0, sizeof(int) * (size_t)B, st) != hipSuccess) return T3D_ERR_LAUNCH;
@@ -187,12 +203,9 @@ extern "C" int t3d_jpeg_decode_roi_u8(const unsigned char* data, long long data_
                                       long long total_segs, const t3d_jpeg_item* items, const int* rects, unsigned char* out,
                                       long long out_bytes, void* work, long long work_bytes, long long total_blocks, int* status, int B,
                                       long long max_lanes, int max_blocks, long long max_runs, void* stream) {
-  if (B < 0 || B > 65535) return T3D_ERR_ARG;
-  if (B == 0) return T3D_OK;
-  if (!data || !infos || !segs || !items || !rects || !out || !work || !status) return T3D_ERR_ARG;
-  if (data_bytes <= 0 || total_segs <= 0 || out_bytes <= 0 || total_blocks <= 0 || total_blocks > (1ll << 40)) return T3D_ERR_ARG;
-  if (max_lanes < 1 || max_blocks < 1 || max_runs < 1) return T3D_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < total_blocks * 192) return T3D_ERR_ARG;
+  const int rc = check_call(B, data && infos && segs && items && rects && out && work && status, data_bytes, total_segs, out_bytes, work,
+                            work_bytes, total_blocks, max_lanes >= 1 && max_blocks >= 1 && max_runs >= 1);
+  if (rc != T3D_OK || B == 0) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(work, 0, (size_t)total_blocks * 128, st) != hipSuccess) return T3D_ERR_LAUNCH;
   if (hipMemsetAsync(status, 0, sizeof(int) * (size_t)B, st) != hipSuccess) return T3D_ERR_LAUNCH;

@@ -1,8 +1,12 @@
 // What ONE LANE of the device JPEG decode does (csrc/jpeg.hip launches it; include/t3d.h states the arithmetic): the checked
 // per-image geometry, the bit reader, the decode of one segment, the inverse DCT of one block, one run of four output pixels;
 // and the same for one pixel rectangle of an image (t3d_jpeg_decode_roi_u8), on a workspace that holds its MCU rectangle only.
+// The segment parser exists once (decode_segment): an item is a window of its image (Roi), a whole frame is the item whose
+// window is the image (whole), and RECT says at compile time whether MCUs outside the window exist.  The IDCT and the pixel
+// arithmetic are shared as they always were.  The item checks (geom, roi_geom) and the four-pixel stores (colour_run,
+// colour_run_roi) stay two each: shared forms of them were built and made whole-frame decodes slower (finding 71).
 // Like csrc/jpeg_index.h it has no HIP include, so the very code the kernels run also compiles for the host, where
-// tools/jpeg_index_check.cpp walks it under the address and undefined-behaviour sanitizers.
+// tools/jpeg_index_check.cpp walks it (tests/test_jpeg_lane_host.py; under the address and undefined-behaviour sanitizers by hand).
 #pragma once
 #include "jpeg_index.h"
 
@@ -132,60 +136,6 @@ struct Bits {
     return (int)((unsigned int)(buf >> cnt) & ((1u << k) - 1u));
   }
 };
-
-// Segment s of a checked image: its MCUs [s * seg_mcus, ...) decoded from the indexed position, the non-zero quantised
-// coefficients stored in natural order into the segment's own (zeroed) blocks.  tab: DC 0, DC 1, AC 0, AC 1.
-// -> false: a code that does not exist (or a run past the block); the rest of the segment's blocks stay zero.
-T3D_JPEG_LANE bool decode_segment(const Geom& g, const t3d_jpeg_huff* tab, const int dci[3], const int aci[3], int s) {
-  const unsigned char zigzag[64] = T3D_JPEG_ZIGZAG;
-  const t3d_jpeg_seg sg = g.segs[s];
-  if (sg.byte >= g.scan_bytes || sg.bit > 7) return false;
-  Bits br;
-  br.p = g.scan, br.n = (unsigned int)g.scan_bytes, br.pos = sg.byte, br.first = 0, br.buf = 0, br.cnt = 0, br.stopped = false;
-  br.refill();
-  br.cnt -= sg.bit;                                     // (the first refill took at least one byte, or stopped and made 32 bits)
-  int pred[3] = {sg.pred[0], sg.pred[1], sg.pred[2]};
-  const int ybl = g.sampling == T3D_JPEG_420 ? 4 : 1;   // luma blocks of an MCU
-  const long long first1 = plane(g, 1).first, first2 = plane(g, 2).first;
-  const int m0 = s * g.seg_mcus, m1 = g.nmcu - m0 > g.seg_mcus ? m0 + g.seg_mcus : g.nmcu;      // s < nseg: m0 < nmcu <= 2^26
-  for (int m = m0; m < m1; ++m) {
-    const int my = m / g.mcus_x, mx = m - my * g.mcus_x;
-    for (int b = 0; b < g.bpm; ++b) {
-      const int c = b < ybl ? 0 : b - ybl + 1;
-      long long blk;
-      if (c == 0) blk = ybl == 4 ? (long long)(2 * my + (b >> 1)) * (2 * g.mcus_x) + 2 * mx + (b & 1) : (long long)m;
-      else blk = (c == 1 ? first1 : first2) + m;
-      short* dst = g.coef + blk * 64;                   // blk < nblocks: one of MCU m's own blocks
-      const t3d_jpeg_huff* hd = tab + dci[c];
-      const t3d_jpeg_huff* ha = tab + aci[c];
-      br.refill();
-      int e = t3d_jpeg_huff_decode(hd, br.peek16());
-      if (e < 0 || (e & 255) > 15) return false;
-      br.cnt -= e >> 8;
-      const int t = e & 255;
-      pred[c] = (int)((unsigned int)pred[c] + (unsigned int)t3d_jpeg_extend(br.get(t), t));      // (wraps; never overflows)
-      if (pred[c] != 0) dst[0] = (short)pred[c];
-      for (int k = 1; k < 64;) {                        // k grows by at least 1 a round
-        br.refill();
-        e = t3d_jpeg_huff_decode(ha, br.peek16());
-        if (e < 0) return false;
-        br.cnt -= e >> 8;
-        const int r = (e >> 4) & 15, sz = e & 15;
-        if (sz == 0) {
-          if (r != 15) break;
-          k += 16;
-          if (k > 64) return false;
-          continue;
-        }
-        k += r;
-        if (k > 63) return false;
-        dst[zigzag[k]] = (short)t3d_jpeg_extend(br.get(sz), sz);
-        ++k;
-      }
-    }
-  }
-  return true;
-}
 
 // ---- inverse DCT -----------------------------------------------------------------------------------------------------------
 // jpeg_idct_islow's butterfly on eight values; SHIFT: 11 (columns) or 18 (rows).  Unsigned arithmetic where a stream that no
@@ -434,9 +384,20 @@ T3D_JPEG_LANE Roi roi_geom(const unsigned char* data, long long data_bytes, cons
   return r;
 }
 
-// Entropy lane t of a checked item (t < rows * per_row) -> the segment it decodes, or -1.  The rectangle's MCU row `my` needs the
-// segments of its MCUs my * mcus_x + mx0 .. + mx1 - 1, at most per_row of them; one that the row above already needed (a segment
-// may straddle rows) is left to that row's lanes, so every needed segment comes up exactly once.
+// geom's result as the item whose window is the image: every pixel, every MCU, every segment, the whole scan.  Only copies, so
+// it may be made before g.ok is looked at (r.g.ok says the same); per_row 0: a whole frame has no lane map, a lane per segment.
+T3D_JPEG_LANE Roi whole(const Geom& g) {
+  Roi r;
+  r.g = g;
+  r.x0 = r.y0 = r.mx0 = r.my0 = r.seg_first = r.per_row = 0;
+  r.x1 = g.w, r.y1 = g.h, r.mx1 = r.img_mcus_x = g.mcus_x, r.my1 = g.mcus_y, r.img_nmcu = g.nmcu, r.seg_count = g.nseg;
+  r.span_first = 0, r.span_bytes = g.scan_bytes;
+  return r;
+}
+
+// Entropy lane t of a checked rectangle item (t < rows * per_row) -> the segment it decodes, or -1.  The rectangle's MCU row `my`
+// needs the segments of its MCUs my * mcus_x + mx0 .. + mx1 - 1, at most per_row of them; one that the row above already needed (a
+// segment may straddle rows) is left to that row's lanes, so every needed segment comes up exactly once.
 T3D_JPEG_LANE int roi_lane_segment(const Roi& r, long long t) {
   const int row = (int)(t / r.per_row), j = (int)(t - (long long)row * r.per_row);
   if (row >= r.my1 - r.my0) return -1;
@@ -447,10 +408,16 @@ T3D_JPEG_LANE int roi_lane_segment(const Roi& r, long long t) {
   return a + j <= b ? a + j : -1;
 }
 
-// decode_segment for segment s (one roi_lane_segment gave) of a checked item: every MCU of the segment up to the rectangle's
-// last is parsed -- bits and DC predictors advance -- and only those inside the rectangle are stored, into their compact blocks.
-T3D_JPEG_LANE bool decode_segment_roi(const Roi& r, const t3d_jpeg_huff* tab, const int dci[3], const int aci[3], int s) {
-  const unsigned char zigzag[64] = T3D_JPEG_ZIGZAG;
+constexpr unsigned char zigzag[64] = T3D_JPEG_ZIGZAG;
+
+// Segment s of a checked item (s < nseg; RECT: one roi_lane_segment gave): its MCUs [s * seg_mcus, ...) of the image parsed from
+// the indexed position -- bits and DC predictors advance --, the non-zero quantised coefficients of those inside the window
+// stored in natural order into their own (zeroed) blocks of the workspace.  tab: DC 0, DC 1, AC 0, AC 1.
+// RECT false: the window is the image (geom), so every MCU is stored, at its image position; true: the parse ends behind the
+// window's last MCU.  (A compile-time choice: the whole-frame lanes do not pay for the window test.)
+// -> false: a code that does not exist (or a run past the block); the rest of the segment's blocks stay zero.
+template <bool RECT>
+T3D_JPEG_LANE bool decode_segment(const Roi& r, const t3d_jpeg_huff* tab, const int dci[3], const int aci[3], int s) {
   const Geom& g = r.g;
   const t3d_jpeg_seg sg = g.segs[s - r.seg_first];      // (roi_geom: the needed segments are among the uploaded ones)
   if (sg.byte < r.span_first || sg.byte - r.span_first >= r.span_bytes || sg.bit > 7) return false;
@@ -458,16 +425,17 @@ T3D_JPEG_LANE bool decode_segment_roi(const Roi& r, const t3d_jpeg_huff* tab, co
   br.p = g.scan, br.n = (unsigned int)r.span_bytes, br.pos = sg.byte, br.first = (unsigned int)r.span_first, br.buf = 0, br.cnt = 0;
   br.stopped = false;
   br.refill();
-  br.cnt -= sg.bit;
+  br.cnt -= sg.bit;                                     // (the first refill took at least one byte, or stopped and made 32 bits)
   int pred[3] = {sg.pred[0], sg.pred[1], sg.pred[2]};
-  const int ybl = g.sampling == T3D_JPEG_420 ? 4 : 1;
+  const int ybl = g.sampling == T3D_JPEG_420 ? 4 : 1;   // luma blocks of an MCU
   const long long first1 = plane(g, 1).first, first2 = plane(g, 2).first;
-  const int last = (r.my1 - 1) * r.img_mcus_x + r.mx1 - 1;                     // the rectangle's last MCU
-  const int m0 = s * g.seg_mcus, end = r.img_nmcu - m0 > g.seg_mcus ? m0 + g.seg_mcus : r.img_nmcu, m1 = lo(end, last + 1);
+  const int last = (r.my1 - 1) * r.img_mcus_x + r.mx1 - 1;                     // the window's last MCU
+  const int m0 = s * g.seg_mcus, end = r.img_nmcu - m0 > g.seg_mcus ? m0 + g.seg_mcus : r.img_nmcu;      // m0 < nmcu <= 2^26
+  const int m1 = RECT ? lo(end, last + 1) : end;
   for (int m = m0; m < m1; ++m) {
     const int my = m / r.img_mcus_x, mx = m - my * r.img_mcus_x;
-    const bool in = mx >= r.mx0 && mx < r.mx1 && my >= r.my0 && my < r.my1;
-    const int cy = my - r.my0, cx = mx - r.mx0, cm = cy * g.mcus_x + cx;      // the MCU within the rectangle
+    const bool in = RECT ? mx >= r.mx0 && mx < r.mx1 && my >= r.my0 && my < r.my1 : true;
+    const int cy = RECT ? my - r.my0 : my, cx = RECT ? mx - r.mx0 : mx, cm = RECT ? cy * g.mcus_x + cx : m;      // within the window
     for (int b = 0; b < g.bpm; ++b) {
       const int c = b < ybl ? 0 : b - ybl + 1;
       long long blk;
@@ -481,9 +449,9 @@ T3D_JPEG_LANE bool decode_segment_roi(const Roi& r, const t3d_jpeg_huff* tab, co
       if (e < 0 || (e & 255) > 15) return false;
       br.cnt -= e >> 8;
       const int t = e & 255;
-      pred[c] = (int)((unsigned int)pred[c] + (unsigned int)t3d_jpeg_extend(br.get(t), t));
+      pred[c] = (int)((unsigned int)pred[c] + (unsigned int)t3d_jpeg_extend(br.get(t), t));      // (wraps; never overflows)
       if (in && pred[c] != 0) dst[0] = (short)pred[c];
-      for (int k = 1; k < 64;) {
+      for (int k = 1; k < 64;) {                        // k grows by at least 1 a round
         br.refill();
         e = t3d_jpeg_huff_decode(ha, br.peek16());
         if (e < 0) return false;

@@ -172,15 +172,21 @@ def collate_jpeg(items):
             torch.from_numpy(counts))
 
 
+def _checked_infos(rows):
+    """rows [(info, segs)] -> their info records as one array; ValueError for a row the device does not decode."""
+    infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
+    for inf, (_, s) in zip(infos, rows):
+        if int(inf['reason']) or int(inf['nseg']) != len(s) or int(inf['nseg']) < 1:
+            raise ValueError('an index row of a file the device does not decode (its reason is set, or its table is incomplete)')
+    return infos
+
+
 def plan_batch(rows, file_offsets, file_sizes, out_offsets):
     """The tables of one t3d_jpeg_decode_u8 call: rows [(info, segs)] of the batch's files, where each file's bytes lie in
     the data buffer and where its frame goes.  -> dict(infos, segs, items (numpy, to upload), total_segs, total_blocks,
     max_segs, max_blocks)."""
-    infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
+    infos = _checked_infos(rows)
     segs = np.concatenate([np.asarray(r[1]) for r in rows] + [np.zeros(0, SEG_DTYPE)])
-    for inf, s in zip(infos, (r[1] for r in rows)):
-        if int(inf['reason']) or int(inf['nseg']) != len(s) or int(inf['nseg']) < 1:
-            raise ValueError('an index row of a file the device does not decode (its reason is set, or its table is incomplete)')
     blocks = infos['mcus_x'].astype(np.int64) * infos['mcus_y'] * np.asarray(_BLOCKS_PER_MCU, np.int64)[infos['sampling']]
     items = np.zeros(len(rows), ITEM_DTYPE)
     items['file_offset'], items['file_bytes'], items['out_offset'] = file_offsets, file_sizes, out_offsets
@@ -190,9 +196,9 @@ def plan_batch(rows, file_offsets, file_sizes, out_offsets):
                 max_segs=int(infos['nseg'].max()), max_blocks=int(blocks.max()))
 
 
-def launch_decode(data, infos, segs, items, plan, out):
-    """Enqueue t3d_jpeg_decode_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items: device uint8
-    tensors holding plan['infos'], ['segs'], ['items'].  -> status, device int32 [B] (0: decoded to the last MCU)."""
+def _launch(entry, data, infos, segs, tables, plan, out, bounds):
+    """Workspace and status vector of one decode call, then the call on the current stream.  tables: the device tensors between
+    `segs` and `out` in the entry's argument list; bounds: the plan's keys of the entry's grid bounds.  -> status, int32 [B]."""
     import ctypes
 
     import torch
@@ -204,10 +210,37 @@ def launch_decode(data, infos, segs, items, plan, out):
         raise RuntimeError('t3d_jpeg_decode_work_bytes failed')
     work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=out.device)
     status = torch.empty(max(B, 1), dtype=torch.int32, device=out.device)
-    N.call('t3d_jpeg_decode_u8', N.ptr(data), data.numel(), N.ptr(infos), N.ptr(segs), plan['total_segs'], N.ptr(items), N.ptr(out),
-           out.numel(), N.ptr(work), work.numel(), plan['total_blocks'], N.ptr(status), B, plan['max_segs'], plan['max_blocks'],
-           N.stream())
+    N.call(entry, N.ptr(data), data.numel(), N.ptr(infos), N.ptr(segs), plan['total_segs'], *[N.ptr(t) for t in tables], N.ptr(out),
+           out.numel(), N.ptr(work), work.numel(), plan['total_blocks'], N.ptr(status), B, *[plan[k] for k in bounds], N.stream())
     return status[:B]
+
+
+def launch_decode(data, infos, segs, items, plan, out):
+    """Enqueue t3d_jpeg_decode_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items: device uint8
+    tensors holding plan['infos'], ['segs'], ['items'].  -> status, device int32 [B] (0: decoded to the last MCU)."""
+    return _launch('t3d_jpeg_decode_u8', data, infos, segs, (items,), plan, out, ('max_segs', 'max_blocks'))
+
+
+def _packed(sizes, dev):
+    """[(h, w)] -> (device uint8 buffer for the RGB images one behind the other, desc int64 [B, 3] = (offset, h, w))."""
+    import torch
+    desc = np.zeros((len(sizes), 3), np.int64)
+    desc[:, 1:] = np.asarray(sizes, np.int64).reshape(-1, 2)
+    nb = desc[:, 1] * desc[:, 2] * 3
+    desc[:, 0] = np.cumsum(nb) - nb
+    dev = torch.device('cuda', torch.cuda.current_device()) if dev is None else torch.device(dev)
+    return torch.empty(max(int(nb.sum()), 1), dtype=torch.uint8, device=dev), desc
+
+
+def _upload_parts(parts, dev):
+    """numpy uint8 arrays -> their device views inside ONE uploaded buffer (each part 16-byte aligned)."""
+    import torch
+    offs = np.concatenate([[0], np.cumsum([-(-p.size // 16) * 16 for p in parts])])
+    host = np.zeros(max(int(offs[-1]), 16), np.uint8)
+    for p, o in zip(parts, offs):
+        host[o:o + p.size] = p
+    d = torch.from_numpy(host).to(dev)
+    return [d[o:o + p.size] for p, o in zip(parts, offs)]
 
 
 def decode_jpeg_batch(files, rows, device=None):
@@ -215,28 +248,14 @@ def decode_jpeg_batch(files, rows, device=None):
     or `index_jpeg` -> (packed device uint8 [sum h * w * 3], desc int64 [B, 3] = (offset, h, w)): the frames as RGB [h][w][3],
     the buffer and table `collate_frames` produces.  One t3d_jpeg_decode_u8 call on the current stream; nothing is read back
     (`decode_jpeg_batch.last_status` holds the call's device status vector)."""
-    import torch
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    arrs = [np.frombuffer(f, np.uint8) for f in files]
-    B = len(arrs)
-    desc = np.zeros((B, 3), np.int64)
-    for i, (inf, _) in enumerate(rows):
-        desc[i, 1], desc[i, 2] = int(inf['h']), int(inf['w'])
-    frame_bytes = desc[:, 1] * desc[:, 2] * 3
-    desc[:, 0] = np.cumsum(frame_bytes) - frame_bytes
-    out = torch.empty(max(int(frame_bytes.sum()), 1), dtype=torch.uint8, device=dev)
-    if B == 0:
+    out, desc = _packed([(int(inf['h']), int(inf['w'])) for inf, _ in rows], device)
+    if not len(files):
         return out, desc
+    arrs = [np.frombuffer(f, np.uint8) for f in files]
     sizes = np.array([a.size for a in arrs], np.int64)
     plan = plan_batch(rows, np.cumsum(sizes) - sizes, sizes, desc[:, 0])
-    parts = [np.concatenate(arrs), plan['infos'].view(np.uint8), plan['segs'].view(np.uint8), plan['items'].view(np.uint8)]
-    offs = np.concatenate([[0], np.cumsum([-(-p.size // 16) * 16 for p in parts])])
-    host = np.zeros(int(offs[-1]), np.uint8)
-    for p, o in zip(parts, offs):
-        host[o:o + p.size] = p
-    d = torch.from_numpy(host).to(dev)
-    data, infos, segs, items = (d[o:o + p.size] for p, o in zip(parts, offs))
-    decode_jpeg_batch.last_status = launch_decode(data, infos, segs, items, plan, out)
+    parts = _upload_parts([np.concatenate(arrs)] + [plan[k].view(np.uint8) for k in ('infos', 'segs', 'items')], out.device)
+    decode_jpeg_batch.last_status = launch_decode(*parts, plan, out)
     return out, desc
 
 
@@ -304,10 +323,7 @@ def plan_roi_batch(rows, plans, data_offsets, out_offsets, spans=None):
     data_offsets: where each item's uploaded scan bytes lie in the data buffer; spans [(first, bytes)]: which bytes of the scan
     those are (None: each plan's own span); out_offsets: where each crop goes.
     -> dict(infos, segs, items, rects (numpy, to upload), total_segs, total_blocks, max_lanes, max_blocks, max_runs)."""
-    infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
-    for inf, (_, s) in zip(infos, rows):
-        if int(inf['reason']) or int(inf['nseg']) != len(s) or int(inf['nseg']) < 1:
-            raise ValueError('an index row of a file the device does not decode (its reason is set, or its table is incomplete)')
+    infos = _checked_infos(rows)
     segs = np.concatenate([np.asarray(r[1][p['seg_first']:p['seg_first'] + p['seg_count']]) for r, p in zip(rows, plans)]
                           + [np.zeros(0, SEG_DTYPE)])
     spans = [p['span'] for p in plans] if spans is None else spans
@@ -327,32 +343,7 @@ def plan_roi_batch(rows, plans, data_offsets, out_offsets, spans=None):
 def launch_decode_roi(data, infos, segs, items, rects, plan, out):
     """Enqueue t3d_jpeg_decode_roi_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items, rects: device
     uint8 tensors holding plan['infos'], ['segs'], ['items'], ['rects'] (`plan_roi_batch`).  -> status, device int32 [B]."""
-    import ctypes
-
-    import torch
-
-    from .. import _native as N
-    B = len(plan['infos'])
-    nbytes = ctypes.c_longlong(0)
-    if N.lib().t3d_jpeg_decode_work_bytes(plan['total_blocks'], ctypes.byref(nbytes)) != 0:
-        raise RuntimeError('t3d_jpeg_decode_work_bytes failed')
-    work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=out.device)
-    status = torch.empty(max(B, 1), dtype=torch.int32, device=out.device)
-    N.call('t3d_jpeg_decode_roi_u8', N.ptr(data), data.numel(), N.ptr(infos), N.ptr(segs), plan['total_segs'], N.ptr(items),
-           N.ptr(rects), N.ptr(out), out.numel(), N.ptr(work), work.numel(), plan['total_blocks'], N.ptr(status), B,
-           plan['max_lanes'], plan['max_blocks'], plan['max_runs'], N.stream())
-    return status[:B]
-
-
-def _upload_parts(parts, dev):
-    """numpy uint8 arrays -> their device views inside ONE uploaded buffer (each part 16-byte aligned)."""
-    import torch
-    offs = np.concatenate([[0], np.cumsum([-(-p.size // 16) * 16 for p in parts])])
-    host = np.zeros(max(int(offs[-1]), 16), np.uint8)
-    for p, o in zip(parts, offs):
-        host[o:o + p.size] = p
-    d = torch.from_numpy(host).to(dev)
-    return [d[o:o + p.size] for p, o in zip(parts, offs)]
+    return _launch('t3d_jpeg_decode_roi_u8', data, infos, segs, (items, rects), plan, out, ('max_lanes', 'max_blocks', 'max_runs'))
 
 
 def decode_jpeg_rois(files, rows, rects, device=None, partial=True):
@@ -360,16 +351,8 @@ def decode_jpeg_rois(files, rows, rects, device=None, partial=True):
     [sum h * w * 3], desc int64 [B, 3] = (offset, h, w)): the rectangles as RGB, the buffer and table `collate_crops` produces
     for the sliced frames.  partial: upload each file's planned byte span only (else its whole scan).  One
     t3d_jpeg_decode_roi_u8 call on the current stream; `decode_jpeg_rois.last_status` holds its device status vector."""
-    import torch
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    B = len(files)
-    desc = np.zeros((B, 3), np.int64)
-    for i, (x0, y0, x1, y1) in enumerate(rects):
-        desc[i, 1], desc[i, 2] = y1 - y0, x1 - x0
-    nb = desc[:, 1] * desc[:, 2] * 3
-    desc[:, 0] = np.cumsum(nb) - nb
-    out = torch.empty(max(int(nb.sum()), 1), dtype=torch.uint8, device=dev)
-    if B == 0:
+    out, desc = _packed([(y1 - y0, x1 - x0) for x0, y0, x1, y1 in rects], device)
+    if not len(files):
         return out, desc
     plans = [plan_roi(inf, sg, *r) for (inf, sg), r in zip(rows, rects)]
     spans = [p['span'] if partial else (0, int(inf['scan_bytes'])) for p, (inf, _) in zip(plans, rows)]
@@ -377,9 +360,9 @@ def decode_jpeg_rois(files, rows, rects, device=None, partial=True):
             for f, (inf, _), (a, n) in zip(files, rows, spans)]
     sizes = np.array([a.size for a in arrs], np.int64)
     plan = plan_roi_batch(rows, plans, np.cumsum(sizes) - sizes, desc[:, 0], spans)
-    data, infos, segs, items, rct = _upload_parts([np.concatenate(arrs)] + [plan[k].reshape(-1).view(np.uint8) for k in
-                                                                            ('infos', 'segs', 'items', 'rects')], dev)
-    decode_jpeg_rois.last_status = launch_decode_roi(data, infos, segs, items, rct, plan, out)
+    parts = _upload_parts([np.concatenate(arrs)] + [plan[k].reshape(-1).view(np.uint8) for k in ('infos', 'segs', 'items', 'rects')],
+                          out.device)
+    decode_jpeg_rois.last_status = launch_decode_roi(*parts, plan, out)
     return out, desc
 
 

@@ -1,7 +1,8 @@
-"""Seeded JPEG test images shared by tests/test_jpeg_host.py and tests/test_gpu_jpeg.py: a smooth field plus noise with a
-constant 0 block, a constant 255 block and alternating 0 / 255 rows, encoded with Pillow over the matrix of sizes, samplings
-and qualities the device decode is pinned on."""
+"""Seeded JPEG test images shared by tests/test_jpeg_host.py, tests/test_jpeg_lane_host.py and tests/test_gpu_jpeg.py: a smooth
+field plus noise with a constant 0 block, a constant 255 block and alternating 0 / 255 rows, encoded with Pillow over the matrix
+of sizes, samplings and qualities the device decode is pinned on; and the truncations and mutations of one of them."""
 import io
+import os
 
 import numpy as np
 from PIL import Image
@@ -50,6 +51,33 @@ def matrix():
                     _matrix.append((f'{h}x{w}_{s}_q{q}_{int(opt)}', encode(image(h, w, n), s, q, opt)))
                     n += 1
     return _matrix
+
+
+_malformed = None
+
+
+def malformed():
+    """(base, [bytes]): one 17 x 33 4:2:0 file, then every truncation of it (the first len(base) entries) and 200 copies with
+    one byte replaced (seeded); made once.  Most are malformed, some mutations still decode."""
+    global _malformed
+    if _malformed is None:
+        base = encode(image(17, 33, 5), '420', 75)
+        corpus = [base[:n] for n in range(len(base))]
+        rng = np.random.default_rng(11)
+        for _ in range(200):
+            m = bytearray(base)
+            m[int(rng.integers(0, len(base)))] = int(rng.integers(0, 256))
+            corpus.append(bytes(m))
+        _malformed = (base, corpus)
+    return _malformed
+
+
+def write_files(out, files):
+    """Writes [bytes] to out/0000.jpg, 0001.jpg, ... (the directory tools/jpeg_index_check.cpp walks)."""
+    os.makedirs(out, exist_ok=True)
+    for i, data in enumerate(files):
+        with open(os.path.join(out, f'{i:04d}.jpg'), 'wb') as f:
+            f.write(data)
 
 
 def pillow(data):

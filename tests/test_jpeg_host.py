@@ -77,19 +77,10 @@ def test_unsupported_files_say_why():
 
 def test_truncated_and_mutated_files_never_crash_and_accepted_tables_stay_inside_the_scan():
     J = _J()
-    base = C.encode(C.image(17, 33, 5), '420', 75)
-    corpus = [base[:n] for n in range(len(base))]
-    rng = np.random.default_rng(11)
-    for _ in range(200):
-        m = bytearray(base)
-        m[int(rng.integers(0, len(base)))] = int(rng.integers(0, 256))
-        corpus.append(bytes(m))
+    base, corpus = C.malformed()
     out = os.environ.get('T3D_JPEG_CORPUS')
     if out:
-        os.makedirs(out, exist_ok=True)
-        for i, data in enumerate(corpus):
-            with open(os.path.join(out, f'{i:04d}.jpg'), 'wb') as f:
-                f.write(data)
+        C.write_files(out, corpus)
     seen = set()
     for data in corpus:
         rc, info, segs = J.index_jpeg(data, 2)

@@ -10,9 +10,9 @@
 // other -- into buffers of exactly the sizes t3d_jpeg_decode_u8 is given; all seg_mcus must give the same pixels.
 // Every accepted file is also decoded rectangle by rectangle (the whole image, 1 x 1 at the corners and the centre, the last row,
 // the last column, interior rectangles on and off MCU and chroma-parity boundaries) through the lane code of
-// t3d_jpeg_decode_roi_u8 -- roi_geom, roi_lane_segment, decode_segment_roi, idct_block on the compact workspace, colour_run_roi
-// -- with only the planned byte span and the needed run of segments copied into heap blocks of exactly their sizes; each must
-// equal the full decode's slice, and every needed segment must come up exactly once.
+// t3d_jpeg_decode_roi_u8 -- roi_geom, roi_lane_segment, the same decode_segment with RECT set, idct_block on the compact
+// workspace, colour_run_roi -- with only the planned byte span and the needed run of segments copied into heap blocks of exactly
+// their sizes; each must equal the full decode's slice, and every needed segment must come up exactly once.
 // --dump writes them to FILE.rgb (h * w * 3 bytes).  Exit status 0: every call returned T3D_OK, T3D_ERR_ARG or
 // T3D_ERR_UNSUPPORTED, every accepted table lies inside its scan and every accepted file decoded with status 0.
 #include <dirent.h>
@@ -27,6 +27,23 @@
 
 namespace L = t3d_jpeg_lane;
 
+// what the kernels set up around the lane calls: the four Huffman tables (DC 0, DC 1, AC 0, AC 1), each component's selectors
+// into them, the quantisation tables widened to int
+struct Tables {
+  t3d_jpeg_huff tab[4];
+  int dci[3], aci[3], quant[192];
+  explicit Tables(const t3d_jpeg_info& info) {
+    for (int t = 0; t < 2; ++t) {
+      t3d_jpeg_build_huff(info.dc_bits[t], info.dc_vals[t], 16, &tab[t]);
+      t3d_jpeg_build_huff(info.ac_bits[t], info.ac_vals[t], 256, &tab[2 + t]);
+    }
+    for (int c = 0; c < 3; ++c) {
+      dci[c] = c < info.ncomp ? info.comp_dc[c] : 0, aci[c] = 2 + (c < info.ncomp ? info.comp_ac[c] : 0);
+      for (int k = 0; k < 64; ++k) quant[64 * c + k] = info.quant[c][k];
+    }
+  }
+};
+
 static bool decode(const unsigned char* data, long long bytes, const t3d_jpeg_info& info, const t3d_jpeg_seg* segs,
                    std::vector<unsigned char>* rgb) {
   t3d_jpeg_item it = {0, bytes, 0, 0, 0, 0};
@@ -38,18 +55,10 @@ static bool decode(const unsigned char* data, long long bytes, const t3d_jpeg_in
   const L::Geom g = L::geom(data, bytes, &info, segs, info.nseg, it, out, out_bytes, work, nblocks);
   bool ok = g.ok;
   if (ok) {
-    t3d_jpeg_huff tab[4];
-    for (int t = 0; t < 2; ++t) {
-      t3d_jpeg_build_huff(info.dc_bits[t], info.dc_vals[t], 16, &tab[t]);
-      t3d_jpeg_build_huff(info.ac_bits[t], info.ac_vals[t], 256, &tab[2 + t]);
-    }
-    int dci[3], aci[3], quant[192];
-    for (int c = 0; c < 3; ++c) {
-      dci[c] = c < g.ncomp ? info.comp_dc[c] : 0, aci[c] = 2 + (c < g.ncomp ? info.comp_ac[c] : 0);
-      for (int k = 0; k < 64; ++k) quant[64 * c + k] = info.quant[c][k];
-    }
-    for (int s = 0; s < g.nseg; ++s) ok = L::decode_segment(g, tab, dci, aci, s) && ok;
-    for (long long b = 0; b < g.nblocks; ++b) L::idct_block(g, quant, b);
+    const Tables T(info);
+    const L::Roi r = L::whole(g);
+    for (int s = 0; s < g.nseg; ++s) ok = L::decode_segment<false>(r, T.tab, T.dci, T.aci, s) && ok;
+    for (long long b = 0; b < g.nblocks; ++b) L::idct_block(g, T.quant, b);
     const long long nrun = ((long long)g.h * g.w + 3) / 4;
     for (long long t = 0; t < nrun; ++t) L::colour_run(g, t, (t & 1) != 0);      // (both store paths)
     rgb->assign(out, out + out_bytes);
@@ -87,16 +96,7 @@ static int decode_rect(const unsigned char* data, const t3d_jpeg_info& info, con
   if (!r.g.ok) {
     printf("%s: rectangle %d %d %d %d refused\n", name, x0, y0, x1, y1), ++bad;
   } else {
-    t3d_jpeg_huff tab[4];
-    for (int t = 0; t < 2; ++t) {
-      t3d_jpeg_build_huff(info.dc_bits[t], info.dc_vals[t], 16, &tab[t]);
-      t3d_jpeg_build_huff(info.ac_bits[t], info.ac_vals[t], 256, &tab[2 + t]);
-    }
-    int dci[3], aci[3], quant[192];
-    for (int c = 0; c < 3; ++c) {
-      dci[c] = c < r.g.ncomp ? info.comp_dc[c] : 0, aci[c] = 2 + (c < r.g.ncomp ? info.comp_ac[c] : 0);
-      for (int k = 0; k < 64; ++k) quant[64 * c + k] = info.quant[c][k];
-    }
+    const Tables T(info);
     std::vector<int> seen((size_t)nseg, 0);
     bool ok = true;
     const long long lanes = (long long)(r.my1 - r.my0) * r.per_row;
@@ -104,13 +104,13 @@ static int decode_rect(const unsigned char* data, const t3d_jpeg_info& info, con
       const int s = L::roi_lane_segment(r, t);
       if (s < 0) continue;
       if (s < s_lo || s > s_hi || seen[s - s_lo]++) printf("%s: segment %d outside the needed run, or twice\n", name, s), ++bad;
-      else ok = L::decode_segment_roi(r, tab, dci, aci, s) && ok;
+      else ok = L::decode_segment<true>(r, T.tab, T.dci, T.aci, s) && ok;
     }
     for (int my = mr.my0; my < mr.my1; ++my)                                  // every segment that owns an MCU of the rectangle came up
       for (int mx = mr.mx0; mx < mr.mx1; ++mx)
         if (!seen[(my * X + mx) / S - s_lo]) printf("%s: segment of MCU %d %d not decoded\n", name, my, mx), ++bad, seen[(my * X + mx) / S - s_lo] = 1;
     if (!ok) printf("%s: rectangle %d %d %d %d did not decode\n", name, x0, y0, x1, y1), ++bad;
-    for (long long b = 0; b < r.g.nblocks; ++b) L::idct_block(r.g, quant, b);
+    for (long long b = 0; b < r.g.nblocks; ++b) L::idct_block(r.g, T.quant, b);
     const long long nrun = (long long)(y1 - y0) * ((x1 - x0 + 3) >> 2);
     for (long long t = 0; t < nrun; ++t) L::colour_run_roi(r, t);
     for (int y = y0; y < y1 && !bad; ++y)
