@@ -102,8 +102,13 @@ def build_detection_loader(cfg):
     `data.train.dataset.{ann_file, img_prefix, min_size, classes}` (a `RepeatDataset` wrapper with times=1; `data.train` itself
     may also be the dataset), `data.val.{ann_file, img_prefix}`; optional `seed`; optional `data.decode` ('host', the default: Pillow in the workers; 'device':
     the workers read file bytes and the frames are decoded on the GPU, dataloaders/jpeg.py), `data.decode_index` (a path stem:
-    the JPEG indexes are kept in `<stem>.train.npy` / `<stem>.val.npy`, built when missing) and `data.decode_seg_mcus`.
-    -> (train, val) `GpuDetectionLoader`s:
+    the JPEG indexes are kept in `<stem>.train.npy` / `<stem>.val.npy`, built when missing) and `data.decode_seg_mcus`;
+    optional `data.cache` ('device': the files, their JPEG index and the annotations are kept in GPU memory and every batch is
+    decoded, drawn and augmented there, dataloaders/detection_arena.py -- it implies the index, `data.decode_index` and
+    `data.decode_seg_mcus` apply as for decode='device', `workers_per_gpu` is not used; any other value raises ValueError) with
+    its budget `data.cache_max_gb` (GiB, default 32: a set that does not fit raises before anything is allocated).
+    -> (train, val) `GpuDetectionLoader`s, or `ArenaDetectionLoader`s with `data.cache = 'device'` (the same tuples bit for bit,
+    but G is the largest box count of the SET, not of the batch; each rank holds the whole arena):
     train yields (imgs uint8 [B,S,S,3], gt_boxes, gt_labels, gt_counts), shuffled by (seed, epoch), last partial batch dropped;
     val is the test pipeline (the resize alone) in dataset order and also yields ori_shapes.  `samples_per_gpu` is PER RANK,
     as in mmdet; under several ranks train uses a DistributedSampler over the one dataset every rank holds and val walks the
@@ -127,6 +132,11 @@ def build_detection_loader(cfg):
         raise NotImplementedError('test_pipeline: only the Resize alone is built')
     world, rk = world_size(), rank()
     decode = _get(data, 'decode', 'host')
+    cache = _get(data, 'cache')
+    if cache is not None and cache != 'device':
+        raise ValueError(f"data.cache = {cache!r}: only 'device' (files, index and annotations kept in GPU memory) or nothing is built")
+    if cache:
+        decode = 'device'
     stem, seg_mcus = _get(data, 'decode_index'), _get(data, 'decode_seg_mcus')
 
     def indexed(d, which):
@@ -137,9 +147,19 @@ def build_detection_loader(cfg):
                                  ann_file=_get(tr, 'ann_file'), decode=decode), 'train')
     sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rk, shuffle=True, seed=seed,
                                                               drop_last=True)
-    train = GpuDetectionLoader(ds, train_tf, bs, sampler=sampler, num_workers=nw, drop_last=True, seed=seed, rank=rk)
     va = _get(data, 'val')
     dv = indexed(ObjectronFrames(_get(va, 'img_prefix'), 'val', cats, ann_file=_get(va, 'ann_file'), decode=decode), 'val')
+    if cache:
+        from ..dataloaders.detection_arena import ArenaDetectionLoader, DetectionArena
+        max_gb = _get(data, 'cache_max_gb', 32) or 32
+        arenas = [DetectionArena(d, max_gb) for d in (ds, dv)]          # (both planned -- budget, box capacity -- before either is filled)
+        for a in arenas:
+            a.fill()
+        train = ArenaDetectionLoader(arenas[0], train_tf, bs, sampler=sampler, drop_last=True, seed=seed, rank=rk)
+        sub = torch.utils.data.Subset(dv, range(rk, len(dv), world)) if world > 1 else dv
+        val = ArenaDetectionLoader(arenas[1], test_tf, bs, indices=range(rk, len(dv), world), seed=seed, rank=rk, dataset=sub)
+        return train, val
+    train = GpuDetectionLoader(ds, train_tf, bs, sampler=sampler, num_workers=nw, drop_last=True, seed=seed, rank=rk)
     if world > 1:
         dv = torch.utils.data.Subset(dv, range(rk, len(dv), world))
     val = GpuDetectionLoader(dv, test_tf, bs, num_workers=nw, seed=seed, rank=rk)

@@ -1,0 +1,390 @@
+"""The detection loader with everything resident on the device: `build_detection_loader` with `data.cache = 'device'`.
+
+`GpuDetectionLoader` over `ObjectronFrames(decode='device')` is bound by its host: a Python loop over the samples runs
+MinIoURandomCrop's search (`DetectionAugmentPipeline.boxes`), DataLoader workers read and collate every file again each epoch,
+and every batch uploads its bytes and index rows.  A cache of pixels cannot exist here -- a frame is 8 MB and every epoch crops
+another part of it -- but a COMPRESSED frame is 0.8 MB and its index 87 KB, and the device decodes a batch from HBM.  So:
+
+`DetectionArena` is filled ONCE from an `ObjectronFrames` that has its `JpegIndex`: every file's bytes in one device uint8 tensor
+(read by at most 16 host threads of this process through rotating pinned staging), the index's `infos` and `segs` as device
+tensors, every image's filtered boxes and labels flattened into device tensors with a start table.  A file the index keeps on
+the host (`reason != 0`) is decoded once, by `dataset._decode_host`, and lies in the same tensor as its RGB frame.  Host numpy
+keeps what planning a batch needs: offsets, sizes, `seg_start`, each frame's h, w, block and segment counts.
+
+`ArenaDetectionLoader` walks the sampler's indices in the main process -- no DataLoader, no worker, no file read.  Per batch
+the host builds, in vectorised numpy, the `t3d_jpeg_item` table (`plan_arena_batch`: `file_offset` and `seg_offset` point into
+the resident tables) and the frame table, uploads both in ONE pinned copy, and enqueues a fixed number of launches:
+`index_select` of the batch's `t3d_jpeg_info` rows, `t3d_jpeg_decode_u8` with data = the arena and segs = the resident table,
+device-to-device copies of host-decoded frames (only files the index refused; none in a set of baseline files),
+`t3d_detect_draw` (csrc/detect_draw.hip: the draws, the crop search, the boxes and the records, bit for bit those of
+`DetectionAugmentPipeline.draw` / `.boxes` / `.records` from the same key) and `t3d_detect_augment_u8`.  The test pipeline takes
+the same route without the draw: records with no flag, `t3d_augment_crops_u8`, boxes scaled and clipped in vectorised numpy,
+`ori_shapes` yielded.
+
+Yields what `GpuDetectionLoader` yields, bit for bit, with ONE difference: G, the second dimension of `gt_boxes` and
+`gt_labels`, is the ARENA's capacity -- the largest box count of any image of the set, at least 1 -- not the batch's largest
+count.  Rows past a count are zero and every consumer reads `gt_counts`.  `prefetch`, the copy stream, the ready event,
+`record_stream`, `sampler`, `__len__`, `last_status`, `dataset` and `batch_size` are `GpuDetectionLoader`'s."""
+import collections
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from .detection import DET_SAMPLE_DTYPE, _CROP_TAG
+from .jpeg import _BLOCKS_PER_MCU, ITEM_DTYPE
+
+__all__ = ['DetectionArena', 'ArenaDetectionLoader', 'plan_arena_batch', 'pipeline_cfg', 'key_words', 'detect_draw_host',
+           'DRAW_CFG_LEN', 'MAX_BOXES']
+
+DRAW_CFG_LEN = 34           # include/t3d.h: cfg of t3d_detect_draw, by position
+MAX_BOXES = 64              # t3d_ssd_multibox_loss and t3d_detect_draw take no more boxes an image
+_MAX_MODES = 16
+assert _CROP_TAG == 0x5D3C0A7E11F2          # csrc/detect_draw.h: TAG_LO, TAG_HI
+
+
+def pipeline_cfg(pipeline):
+    """A compiled `DetectionAugmentPipeline` -> the float64 [34] `cfg` of t3d_detect_draw (include/t3d.h lists the positions)."""
+    c = np.zeros(DRAW_CFG_LEN, np.float64)
+    ph = pipeline.photo or dict(delta=0., contrast=(1., 1.), saturation=(1., 1.), hue=0.)
+    c[0] = pipeline.photo is not None
+    c[1], c[2:4], c[4:6], c[6] = ph['delta'], ph['contrast'], ph['saturation'], ph['hue']
+    c[7] = pipeline.p_rot or 0.0
+    ex = pipeline.expand or dict(ratio=(1., 1.), p=0.)
+    c[8:10], c[10] = ex['ratio'], ex['p']
+    if pipeline.crop is not None:
+        modes = pipeline.crop['modes']
+        if len(modes) > _MAX_MODES:
+            raise NotImplementedError(f'MinIoURandomCrop: {len(modes)} modes (t3d_detect_draw takes {_MAX_MODES})')
+        c[11], c[12], c[14] = 1, pipeline.crop['min_size'], len(modes)
+        c[15:15 + len(modes)] = modes
+    # `iou.min() < mode`: a float32 against a Python float -- float32 where the installed numpy treats the Python float as weak
+    c[13] = (np.float32(1) + 0.1).dtype == np.float32
+    c[31], c[32], c[33] = pipeline.p_flip, pipeline.size[0], pipeline.size[1]
+    return c
+
+
+def key_words(key):
+    """(seed, epoch, rank, batch) -> the uint32 words numpy's SeedSequence makes of those integers: each as its 32-bit words,
+    low word first, at least one."""
+    out = []
+    for v in key:
+        v = int(v)
+        if v < 0:
+            raise ValueError(f'a key holds non-negative integers, not {v}')
+        out.append(v & 0xFFFFFFFF)
+        v >>= 32
+        while v:
+            out.append(v & 0xFFFFFFFF)
+            v >>= 32
+    if len(out) > 16:
+        raise ValueError(f'the key makes {len(out)} words; t3d_detect_draw takes 16')
+    return np.asarray(out, np.uint32)
+
+
+def detect_draw_host(pipeline, key, frames, boxes, labels, box_start, G):
+    """`t3d_detect_draw_host`: the draws, boxes and records of one batch on the CPU (no GPU is touched).  frames int64 [B, 4] =
+    (offset, h, w, dataset index); boxes float32 [n, 4], labels int32 [n], box_start int64 [images + 1].
+    -> (records [B] DET_SAMPLE_DTYPE, gt_boxes float32 [B, G, 4], gt_labels int32 [B, G], gt_counts int32 [B], diag int32 [B, 2])."""
+    from .. import _native as N
+    cfg, words = pipeline_cfg(pipeline), key_words(key)
+    frames = np.ascontiguousarray(frames, np.int64).reshape(-1, 4)
+    boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
+    labels, box_start = np.ascontiguousarray(labels, np.int32), np.ascontiguousarray(box_start, np.int64)
+    B = len(frames)
+    rec = np.full(B, 0, DET_SAMPLE_DTYPE)
+    gb, gl = np.full((B, G, 4), np.nan, np.float32), np.full((B, G), -1, np.int32)
+    gc, diag = np.full(B, -1, np.int32), np.full((B, 2), -7, np.int32)
+    rc = N.lib().t3d_detect_draw_host(cfg.ctypes.data, len(cfg), words.ctypes.data, len(words), frames.ctypes.data, B, boxes.ctypes.data,
+                                      labels.ctypes.data, box_start.ctypes.data, len(box_start) - 1, len(labels), int(G), rec.ctypes.data,
+                                      gb.ctypes.data, gl.ctypes.data, gc.ctypes.data, diag.ctypes.data, None)
+    if rc != 0:
+        raise RuntimeError(f't3d_detect_draw_host failed with code {rc}')
+    return rec, gb, gl, gc, diag
+
+
+def plan_arena_batch(idx, file_off, size, seg_start, h, w, blocks, nseg):
+    """Pure numpy: the tables of one t3d_jpeg_decode_u8 call over RESIDENT files.  idx: the batch's dataset indices (files the
+    device decodes); the other arguments are the arena's per-file host arrays.  -> dict(items [len(idx)] ITEM_DTYPE, frames int64
+    [len(idx), 4] = (out offset, h, w, dataset index), out_bytes, total_blocks, max_segs, max_blocks).  `out_offset` and
+    `block_offset` are prefix sums of the known frame sizes -- what `plan_batch` computes from the rows themselves --
+    `file_offset` and `seg_offset` point into the resident tables."""
+    idx = np.asarray(idx, np.int64).reshape(-1)
+    hh, ww = h[idx].astype(np.int64), w[idx].astype(np.int64)
+    nb = hh * ww * 3
+    bl = blocks[idx].astype(np.int64)
+    items = np.zeros(len(idx), ITEM_DTYPE)
+    items['file_offset'], items['file_bytes'], items['seg_offset'] = file_off[idx], size[idx], seg_start[idx]
+    items['out_offset'], items['block_offset'] = np.cumsum(nb) - nb, np.cumsum(bl) - bl
+    frames = np.stack([items['out_offset'], hh, ww, idx], 1) if len(idx) else np.zeros((0, 4), np.int64)
+    return dict(items=items, frames=frames, out_bytes=int(nb.sum()), total_blocks=int(bl.sum()),
+                max_segs=int(nseg[idx].max()) if len(idx) else 1, max_blocks=int(bl.max()) if len(idx) else 1)
+
+
+class DetectionArena:
+    """A whole `ObjectronFrames` resident on the device (the module's docstring).  `plan()` is host only: it reads nothing but
+    the index and the annotations, decodes the files the index keeps on the host, and raises ValueError when the set does not
+    fit `max_gb` (GiB, the meaning and default of the regression cache's `data.cache_max_gb`) or an image has more than 64
+    boxes -- before anything is allocated.  `fill()` then reads the files and uploads everything."""
+    STAGING = 64 << 20          # bytes of one pinned staging buffer (a larger file gets a buffer of its own size)
+    NBUF = 3
+
+    def __init__(self, frames, max_gb=32, threads=16):
+        if getattr(frames, 'index', None) is None:
+            raise RuntimeError('DetectionArena needs the JPEG index of its ObjectronFrames: call build_index() first')
+        self.frames, self.max_gb, self.threads = frames, max_gb, max(1, min(int(threads), 16))
+        self.data = None
+        self.plan()
+
+    def plan(self):
+        fr, index = self.frames, self.frames.index
+        n = len(fr)
+        index.check(fr.root)                                     # a changed size or mtime raises, naming the file
+        self.kind = (np.asarray(index.reason) != 0).astype(np.int64)          # 1: the arena holds the host-decoded RGB frame
+        infos = index.infos
+        self.h, self.w = np.array(infos['h'], np.int64), np.array(infos['w'], np.int64)
+        self.size = np.array(index.size, np.int64)
+        self._host_frames = {}
+        for i in np.flatnonzero(self.kind):
+            f = np.ascontiguousarray(fr._decode_host(fr.root + '/' + fr.files[i]), np.uint8)
+            self._host_frames[int(i)] = f
+            self.h[i], self.w[i], self.size[i] = f.shape[0], f.shape[1], f.size
+        self.file_off = np.cumsum(self.size) - self.size
+        self.seg_start = np.array(index.seg_start[:-1], np.int64)
+        dev = self.kind == 0
+        self.nseg = np.where(dev, infos['nseg'], 0).astype(np.int64)
+        self.blocks = np.where(dev, infos['mcus_x'].astype(np.int64) * infos['mcus_y']
+                               * np.asarray(_BLOCKS_PER_MCU, np.int64)[np.clip(infos['sampling'], 0, 2)], 0)
+        counts = np.array([len(l) for l in fr._labels], np.int64).reshape(-1)
+        self.box_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.boxes = np.concatenate([np.asarray(b, np.float32).reshape(-1, 4) for b in fr._boxes] + [np.zeros((0, 4), np.float32)])
+        self.labels = np.concatenate([np.asarray(l, np.int32).reshape(-1) for l in fr._labels] + [np.zeros(0, np.int32)])
+        self.G = int(max(counts.max() if n else 0, 1))
+        if self.G > MAX_BOXES:
+            i = int(counts.argmax())
+            raise ValueError(f'{fr.files[i]} has {self.G} boxes; t3d_ssd_multibox_loss takes {MAX_BOXES} an image')
+        self.bytes = (int(self.size.sum()) + infos.size * infos.dtype.itemsize + len(index.segs) * index.segs.dtype.itemsize
+                      + self.boxes.nbytes + self.labels.nbytes + self.box_start.nbytes)
+        budget = int(float(self.max_gb) * 2 ** 30)
+        if self.bytes > budget:
+            raise ValueError(f'data.cache: {n} files and their index need {self.bytes} bytes ({self.bytes / 2 ** 30:.3f} GiB), over the '
+                             f'budget data.cache_max_gb = {self.max_gb} ({budget} bytes); there is no partial cache')
+
+    def __len__(self):
+        return len(self.frames)
+
+    def fill(self, device=None):
+        """Read every file (at most 16 threads of this process, rotating pinned staging) and upload the tables.  -> self."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("data.cache = 'device' keeps the files on the GPU (no CPU fallback)")
+        fr, index = self.frames, self.frames.index
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        total = int(self.size.sum())
+        self.data = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        # chunks of consecutive files that fit one staging buffer
+        chunks, start, acc = [], 0, 0
+        for i, s in enumerate(self.size):
+            if acc and acc + s > self.STAGING:
+                chunks.append((start, i))
+                start, acc = i, 0
+            acc += int(s)
+        if len(self.size):
+            chunks.append((start, len(self.size)))
+        slots = [[None, None] for _ in range(self.NBUF)]
+
+        def read(i, view, base):
+            at, n = int(self.file_off[i] - base), int(self.size[i])
+            if self.kind[i]:
+                view[at:at + n] = self._host_frames[i].reshape(-1)
+                return
+            path = os.path.join(str(fr.root), fr.files[i])
+            with open(path, 'rb') as f:
+                got = f.readinto(memoryview(view[at:at + n]))
+                more = f.read(1)
+            if got != n or more:
+                raise RuntimeError(f'{path} changed since it was indexed ({n} bytes in the index): rebuild the index')
+        with ThreadPoolExecutor(max_workers=self.threads) as ex:
+            for turn, (a, b) in enumerate(chunks):
+                slot = slots[turn % self.NBUF]
+                base, nbytes = int(self.file_off[a]), int(self.size[a:b].sum())
+                if slot[1] is not None:
+                    slot[1].synchronize()          # the upload that last read this buffer has completed
+                if slot[0] is None or slot[0].numel() < nbytes:
+                    slot[0] = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
+                view = slot[0].numpy()
+                list(ex.map(lambda i: read(i, view, base), range(a, b)))
+                self.data[base:base + nbytes].copy_(slot[0][:nbytes], non_blocking=True)
+                slot[1] = torch.cuda.Event()
+                slot[1].record()
+        self._host_frames = {}
+
+        def up(a):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(16, np.uint8)).to(dev)
+        self.infos = up(np.asarray(index.infos)).view(-1, index.infos.dtype.itemsize) if len(fr) else up(np.zeros(0, np.uint8))
+        self.segs = up(np.asarray(index.segs))
+        self.d_boxes, self.d_labels, self.d_box_start = up(self.boxes), up(self.labels), up(self.box_start)
+        torch.cuda.synchronize(dev)                # every later stream finds the tables complete
+        return self
+
+
+class ArenaDetectionLoader:
+    """Batches for the detector from a filled `DetectionArena` (the module's docstring): the tuples of `GpuDetectionLoader`, with
+    G = `arena.G`.  indices: the dataset indices this loader walks, in order, when there is no sampler (None: all of them);
+    `dataset` is what `GpuDetectionLoader.dataset` would be (the frames, or the Subset of them)."""
+    NBUF = 3
+
+    def __init__(self, arena, pipeline, batch_size, sampler=None, indices=None, drop_last=False, seed=0, rank=0, prefetch=1,
+                 dataset=None):
+        if arena.data is None:
+            raise RuntimeError('ArenaDetectionLoader needs a filled arena: call DetectionArena.fill() first')
+        self.arena, self.pipeline, self.batch_size = arena, pipeline, int(batch_size)
+        self.seed, self.rank, self.prefetch, self.drop_last = int(seed), int(rank), int(prefetch), bool(drop_last)
+        self.sampler = sampler
+        self.indices = np.arange(len(arena), dtype=np.int64) if indices is None else np.asarray(list(indices), np.int64)
+        self.dataset = arena.frames if dataset is None else dataset
+        self.decode, self.last_status = 'arena', None
+        self._cfg = pipeline_cfg(pipeline)
+        self._slots = [[None, None] for _ in range(self.NBUF)]
+        self._turn = 0
+        self._copy_stream = None
+
+    def _order(self):
+        return np.fromiter(iter(self.sampler), np.int64) if self.sampler is not None else self.indices
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.indices)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _staging(self, nbytes):
+        import torch
+        slot = self._slots[self._turn]
+        self._turn = (self._turn + 1) % self.NBUF
+        if slot[1] is not None:
+            slot[1].synchronize()
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(max(nbytes, 1 << 14), dtype=torch.uint8).pin_memory()
+        return slot
+
+    def host_plan(self, idx):
+        """The host half of one batch, vectorised numpy only.  idx: the batch's dataset indices.  -> (parts: the uint8 arrays of
+        the one upload -- frames | items | gather indices [| records | boxes | labels | counts | shapes for the test pipeline] --
+        plan of the device-decoded files, positions of the host-decoded frames)."""
+        from .objectron import AUG_SAMPLE_DTYPE
+        A = self.arena
+        idx = np.asarray(idx, np.int64)
+        B = len(idx)
+        hh, ww = A.h[idx], A.w[idx]
+        nb = hh * ww * 3
+        out_off = np.cumsum(nb) - nb
+        frames = np.stack([out_off, hh, ww, idx], 1)
+        on_dev = np.flatnonzero(A.kind[idx] == 0)
+        plan = plan_arena_batch(idx[on_dev], A.file_off, A.size, A.seg_start, A.h, A.w, A.blocks, A.nseg)
+        plan['items']['out_offset'] = out_off[on_dev]
+        plan['out_bytes'] = int(nb.sum())
+        parts = [frames.reshape(-1).view(np.uint8), plan['items'].view(np.uint8), idx[on_dev].view(np.uint8)]
+        if not self.pipeline.random:
+            oh, ow = self.pipeline.size
+            G = A.G
+            rec = np.zeros(B, AUG_SAMPLE_DTYPE)              # flags 0: the resize alone
+            rec['offset'], rec['h'], rec['w'] = out_off, hh, ww
+            start, cnt = A.box_start[idx], A.box_start[idx + 1] - A.box_start[idx]
+            row = np.repeat(np.arange(B), cnt)
+            col = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+            src = np.repeat(start, cnt) + col
+            sc = np.stack([ow / ww, oh / hh, ow / ww, oh / hh], 1).astype(np.float32)          # mmdet's Resize: scale, then clip
+            gb, gl = np.zeros((B, G, 4), np.float32), np.zeros((B, G), np.int32)
+            gb[row, col] = np.minimum(np.maximum(A.boxes[src] * sc[row], np.float32(0)), np.array([ow, oh, ow, oh], np.float32))
+            gl[row, col] = A.labels[src]
+            parts += [rec.view(np.uint8), gb.reshape(-1).view(np.uint8), gl.reshape(-1).view(np.uint8), cnt.astype(np.int32).view(np.uint8),
+                      np.stack([hh, ww], 1).astype(np.int32).reshape(-1).view(np.uint8)]
+        return parts, plan, np.flatnonzero(A.kind[idx] != 0), frames
+
+    def finish(self, idx, key_tail, prefetch=None):
+        """The batch of dataset indices `idx` -> the device tuple, enqueued on the copy stream (prefetch >= 1: the ready event is
+        appended) or on the current stream (prefetch 0)."""
+        import torch
+
+        from .. import _native as N
+        from .jpeg import _launch
+        prefetch = self.prefetch if prefetch is None else prefetch
+        A = self.arena
+        parts, plan, on_host, frames = self.host_plan(idx)
+        B, G = len(idx), A.G
+        oh, ow = self.pipeline.size
+        offs = np.concatenate([[0], np.cumsum([(p.size + 15) // 16 * 16 for p in parts])])
+        total = int(offs[-1])
+        slot = self._staging(total)
+        host = slot[0]
+        for p, o in zip(parts, offs):
+            host[o:o + p.size].numpy()[...] = p
+        dev = A.data.device
+        stream = torch.cuda.current_stream(dev)
+        if prefetch > 0:
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(device=dev)
+            stream = self._copy_stream
+        with torch.cuda.stream(stream):
+            meta = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+            meta[:total].copy_(host[:total], non_blocking=True)
+            slot[1] = torch.cuda.Event()
+            slot[1].record(stream)
+
+            def part(k, dtype, *shape):
+                return meta[offs[k]:offs[k] + parts[k].size].view(dtype).view(*shape)
+            imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
+            src = torch.empty(max(plan['out_bytes'], 1), dtype=torch.uint8, device=dev)
+            n_dev = len(plan['items'])
+            if n_dev:
+                infos = A.infos.index_select(0, part(2, torch.int64, n_dev))
+                call = dict(infos=plan['items'], total_segs=A.segs.numel() // 16, total_blocks=plan['total_blocks'],
+                            max_segs=plan['max_segs'], max_blocks=plan['max_blocks'])
+                self.last_status = _launch('t3d_jpeg_decode_u8', A.data, infos, A.segs, (part(1, torch.uint8, -1),), call, src,
+                                           ('max_segs', 'max_blocks'))
+            else:
+                self.last_status = torch.zeros(0, dtype=torch.int32, device=dev)
+            for k in on_host:                      # frames the host had to decode (files the index refused) lie in the arena as they are
+                at, to, n = int(A.file_off[idx[k]]), int(frames[k, 0]), int(A.size[idx[k]])
+                src[to:to + n].copy_(A.data[at:at + n], non_blocking=True)
+            if self.pipeline.random:
+                epoch = int(getattr(self.sampler, 'epoch', 0))
+                words = key_words((self.seed, epoch, self.rank) + tuple(key_tail))
+                sizes = [B * 80, B * G * 16, B * G * 4, B * 4, B * 8]
+                o = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])
+                res = torch.empty(int(o[-1]), dtype=torch.uint8, device=dev)
+                rec, gb, gl, gc, diag = (res[o[k]:o[k] + sizes[k]] for k in range(5))
+                N.call('t3d_detect_draw', self._cfg.ctypes.data, len(self._cfg), words.ctypes.data, len(words), N.ptr(part(0, torch.uint8, -1)),
+                       B, N.ptr(A.d_boxes), N.ptr(A.d_labels), N.ptr(A.d_box_start), len(A), len(A.labels), G, N.ptr(rec), N.ptr(gb),
+                       N.ptr(gl), N.ptr(gc), N.ptr(diag), N.stream())
+                N.call('t3d_detect_augment_u8', N.ptr(src), src.numel(), N.ptr(rec), N.ptr(imgs), B, oh, ow, N.stream())
+                out = [imgs, gb.view(torch.float32).view(B, G, 4), gl.view(torch.int32).view(B, G), gc.view(torch.int32)]
+            else:
+                N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(part(3, torch.uint8, -1)), N.ptr(imgs), B, oh, ow, N.stream())
+                out = [imgs, part(4, torch.float32, B, G, 4), part(5, torch.int32, B, G), part(6, torch.int32, B), part(7, torch.int32, B, 2)]
+        if prefetch > 0:
+            ready = torch.cuda.Event()
+            ready.record(stream)
+            out.append(ready)
+        return tuple(out)
+
+    def __iter__(self):
+        import torch
+        order = self._order()
+        nb = len(self)
+        pending, b = collections.deque(), 0
+        while True:
+            while b < nb and len(pending) <= self.prefetch:
+                pending.append(self.finish(order[b * self.batch_size:(b + 1) * self.batch_size], (b,)))
+                b += 1
+            if not pending:
+                return
+            out = pending.popleft()
+            if self.prefetch > 0:
+                *out, ready = out
+                consumer = torch.cuda.current_stream(out[0].device)
+                consumer.wait_event(ready)
+                for t in out[:2]:                # (boxes, labels, counts and shapes share one allocation)
+                    t.record_stream(consumer)
+                out = tuple(out)
+            yield out

@@ -400,6 +400,50 @@ typedef struct {
 int t3d_detect_augment_u8(const unsigned char* src, long long src_bytes, const void* records, unsigned char* out, int B, int oh,
                           int ow, void* stream);
 
+/* t3d_detect_draw: the records t3d_detect_augment_u8 takes and the batch's ground truth, made ON THE DEVICE in one launch from
+ * tables that live there (csrc/detect_draw.hip, csrc/detect_draw.h; torchdet3d/dataloaders/detection_arena.py).  It does what
+ * DetectionAugmentPipeline.draw, .boxes and .records do on the host (torchdet3d/dataloaders/detection.py) and gives THEIR
+ * RESULTS BIT FOR BIT from the same key; tests/test_detect_draw_host.py holds t3d_detect_draw_host to them.
+ * t3d_detect_draw_host is the same arithmetic on the CPU: the same arguments, every pointer a HOST pointer, `stream` ignored;
+ * HOST ONLY, no HIP call, never initialises the GPU.
+ *   cfg [n_cfg = 34] doubles, HOST memory (both entry points): the compiled pipeline, by position
+ *        0  PhotoMetricDistortion present (0 / 1)     1  brightness_delta     2, 3  contrast_range     4, 5  saturation_range
+ *        6  hue_delta     7  probability of the quarter turn     8, 9  Expand's ratio_range (1, 1 without)     10  Expand's prob
+ *        11  MinIoURandomCrop present     12  min_crop_size     13  1: `iou.min() < mode` compares in float32 (numpy >= 2: a
+ *        Python float is weak), 0: in float64     14  number of crop modes, <= 16     15 .. 30  the modes (1 = the whole canvas;
+ *        with a crop one of them must be 1)     31  flip_ratio     32  oh     33  ow
+ *   key [n_key <= 16] uint32, HOST memory: the words numpy's SeedSequence makes of (seed, epoch, rank, batch) -- each integer
+ *        as its 32-bit words, low word first, at least one
+ *   frames int64 [B, 4]    per sample (byte offset of the decoded frame, h, w, dataset index)
+ *   boxes float32 [n_boxes, 4], labels int32 [n_boxes], box_start int64 [n_images + 1]: image j owns the rows
+ *        box_start[j] .. box_start[j + 1] - 1
+ *   records [B] t3d_det_sample (byte-identical to records()); gt_boxes float32 [B, G, 4] in output pixels; gt_labels int32 [B, G];
+ *   gt_counts int32 [B]; every row past a count is zero.  diag int32 [B, 2]: the index of the crop mode that returned (-1
+ *   without a crop) and the number of uniforms the crop search drew (saturated at 2^31 - 1).
+ * Random numbers: numpy's.  SeedSequence (pool of 4 words, hash-mix constants 0x43b0d7e5 / 0x931e8875 / 0x8b51f9dd / 0x58f38ded /
+ * 0xca01f9dd / 0x4973f715, generate_state of eight words) seeds PCG64 (state = state * 0x2360ED051FC65DA44385DF649FCCF645 + inc
+ * in 128 bits, XSL-RR output); random() = (next64 >> 11) * 2^-53.  The batch's generator is default_rng(key).random((B, 18)):
+ * sample i owns outputs 18 i .. 18 i + 17 (columns: DetectionAugmentPipeline.draw) and reaches them by the LCG's jump-ahead.
+ * The crop search of sample i draws from its own generator keyed (*key, 0x0A7E11F2, 0x5D3C, i).
+ * Arithmetic: float64 where the host computes with Python floats (the photometric parameters before their cast, Expand's
+ * ratio, canvas and paste position, the crop's new_w / new_h, aspect test, left / top and their truncation, the ow / cw scale
+ * before its cast), float32 where it computes on float32 arrays (the turn, the shift, IoU with max(union, 1e-6) and its
+ * division, centres, clip, scale, flip); every operation rounded on its own, no fused multiply-add.  Loops: 50 tries a mode, a
+ * fresh mode after 50 failures, without bound; mode 1 returns the whole canvas.
+ * One sample a wave, lane 0 walks: the launch lasts as long as its longest search.
+ * T3D_ERR_ARG, nothing launched: a NULL pointer, n_cfg != 34, n_key < 1 or > 16, B < 0 or > 65535, G < 1 or > 64, negative
+ * table sizes, oh or ow < 1, a ratio_range outside 1 <= lo <= hi <= 64, with a crop: no mode or more than 16, min_crop_size
+ * outside (0, 1], no mode equal to 1.  B == 0 returns T3D_OK.
+ * A bad sample gets a ZERO record (a zero image, by t3d_detect_augment_u8's rule), count 0 and diag (-1, 0), and the others are
+ * left alone: h or w < 1 or > 2^24, offset < 0, a dataset index outside [0, n_images), a box range outside [0, n_boxes] or
+ * longer than G.  Nothing is read outside the tables or written outside the sample's own rows. */
+int t3d_detect_draw(const double* cfg, int n_cfg, const unsigned int* key, int n_key, const long long* frames, int B,
+                    const float* boxes, const int* labels, const long long* box_start, long long n_images, long long n_boxes, int G,
+                    void* records, float* gt_boxes, int* gt_labels, int* gt_counts, int* diag, void* stream);
+int t3d_detect_draw_host(const double* cfg, int n_cfg, const unsigned int* key, int n_key, const long long* frames, int B,
+                         const float* boxes, const int* labels, const long long* box_start, long long n_images, long long n_boxes,
+                         int G, void* records, float* gt_boxes, int* gt_labels, int* gt_counts, int* diag, void* stream);
+
 /* Baseline JPEG frames decoded on the device from a per-file index (csrc/jpeg_index.h, csrc/jpeg.hip; replaces the workers'
  * Pillow decode in front of t3d_detect_augment_u8).  Huffman decoding is serial inside a scan and Objectron frames carry no
  * restart markers, so ONCE PER FILE the host walks the scan (t3d_jpeg_index) and records where every seg_mcus-th MCU starts;
