@@ -7,3 +7,5 @@ from .ie_wrappers import Regressor, Detector
 from .tracking_tools import IOUTracker, TrackedObj
 from .draw import DrawStyle, draw_overlays, draw_kp
 from .pipeline import FramePipeline
+from .jpeg_encode import JpegEncoder
+from .mjpeg import MjpegWriter, MjpegReader

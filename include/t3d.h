@@ -581,6 +581,86 @@ int t3d_jpeg_decode_roi_u8(const unsigned char* data, long long data_bytes, cons
                            long long out_bytes, void* work, long long work_bytes, long long total_blocks, int* status, int B,
                            long long max_lanes, int max_blocks, long long max_runs, void* stream);
 
+/* Baseline JPEG ENCODE on the device (csrc/jpeg_encode.h, csrc/jpeg_encode.hip): B RGB uint8 frames [B][h][w][3] of one size ->
+ * B baseline JFIF files, the third leg beside t3d_jpeg_index and t3d_jpeg_decode_u8 (the files carry no restart markers: the
+ * index accepts them with reason 0).  torchdet3d/utils/jpeg_encode.py wraps it, torchdet3d/utils/mjpeg.py puts the files into
+ * a Motion-JPEG AVI (the reference's cv.VideoWriter, scripts/demo.py:50-54, 83-84).
+ *
+ * DEFINITION: libjpeg-turbo's default compression path as Pillow drives it, Image.save(format='JPEG', quality=q,
+ * subsampling=s) with optimize and progressive off; restated in numpy by tests/jpeg_encode_ref.py.  The FILES are Pillow's on
+ * libjpeg-turbo BYTE FOR BYTE (pinned by tests/test_jpeg_encode_host.py and tests/test_gpu_jpeg_encode.py).  Sampling is
+ * T3D_JPEG_444 or T3D_JPEG_420; grey output, 4:2:2, optimised Huffman tables and restart intervals are out of scope.
+ *   layout     SOI; APP0 FF E0 00 10 'JFIF\0' 01 01 00 00 01 00 01 00 00; two DQT, each FF DB 00 43, the id 0 / 1, 64 bytes in
+ *              zig-zag order; SOF0 FF C0 00 11 08 hh hh ww ww 03 | 01 SS 00 | 02 11 01 | 03 11 01, SS = 22 (4:2:0) / 11 (4:4:4);
+ *              four DHT in the order DC0 (00), AC0 (10), DC1 (01), AC1 (11): the Annex K tables (lengths 1F, B5, 1F, B5);
+ *              SOS FF DA 00 0C 03 01 00 02 11 03 11 00 3F 00; the scan; FF D9.  The header is 623 bytes.
+ *   quant      Annex K luminance / chrominance tables t, s = 5000 / q (q < 50) or 200 - 2q, entry = clip((t s + 50) / 100, 1,
+ *              255) in integers, q = 1 .. 100.
+ *   colour     jccolor, FIX(x) = int(x * 65536 + 0.5):  Y = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16,
+ *              Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B + (128 << 16) + 32767) >> 16,
+ *              Cr = (FIX(.5) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16.
+ *   edges      Y and 4:4:4 chroma: a real block's samples beyond the image replicate the last column and the last row.  4:2:0
+ *              chroma: full-resolution columns are replicated to 16 ceil(w / 16), full-resolution rows only to even h; then
+ *              (a + b + c + d + bias) >> 2 with bias 1 on even output columns, 2 on odd ones; then the last DOWNSAMPLED row is
+ *              replicated down to 8 ceil(h / 16) rows (not the same as replicating full-resolution rows).
+ *   FDCT       jfdctint.c (islow) on sample - 128 in int32, CONST_BITS 13, PASS1_BITS 2, FIX(x) = int(x * 8192 + 0.5) of
+ *              0.298631336 0.390180644 0.541196100 0.765366865 0.899976223 1.175875602 1.501321110 1.847759065 1.961570560
+ *              2.053119869 2.562915447 3.072711026; rows first -- outputs 0 and 4 are << 2, the rest (x + 2^10) >> 11 --, then
+ *              columns -- outputs 0 and 4 are (x + 2) >> 2, the rest (x + 2^14) >> 15.
+ *   quantise   d = 8 * table entry:  sign(c) * ((|c| + d / 2) / d).
+ *   dummies    4:2:0 luma only: a block with block row >= ceil(h / 8) or block column >= ceil(w / 8) is not transformed; its
+ *              AC coefficients are zero and its DC is that of the block before it in the MCU (a missing right block: its left
+ *              neighbour; both blocks of a missing bottom row: the last block of the row above, real or dummy).
+ *   entropy    one interleaved scan, MCUs in raster order, the DC difference of a component predicted across the whole scan;
+ *              category + extra bits, ZRL (F0) for runs above 15, EOB (00) when the tail is zero; bits MSB first, a 00 behind
+ *              every FF byte, the last byte padded with 1 bits.
+ *
+ * t3d_jpeg_encode_setup (HOST ONLY like t3d_jpeg_index: no HIP call): fills *out -- the header bytes, the divisors, the four
+ * Huffman code tables, the geometry.  T3D_ERR_ARG: out NULL, h or w outside 1 .. 65535, quality outside 1 .. 100, a sampling
+ * other than T3D_JPEG_444 / T3D_JPEG_420.
+ * t3d_jpeg_encode_work_bytes: the work buffer of one call with these arguments.  T3D_ERR_ARG: bytes NULL, B < 0 or > 65535, h,
+ * w, sampling as above, seg_mcus < 1, cap_bytes below header + 2 (625) or above 2^40.
+ * t3d_jpeg_encode_u8: ONE memset and SEVEN kernels on `stream` whatever B is; no allocation, no host synchronisation, no
+ * read-back; the same bytes on every run (integer arithmetic; lanes that share a 32-bit word of the stream OR their bits in).
+ *   transform  a lane per 8x8 block: colour, edge rule, downsample, FDCT, quantise -> int16 [block in scan order][64 in
+ *              zig-zag order]; the dummy blocks are written here (their DC needs only the sum of the source block's samples)
+ *   count      a lane per SEGMENT of seg_mcus consecutive MCUs (as the decoder's lanes are cut): the exact bit length of its
+ *              codes, DC predictors read from the coefficient array by index; then a per-frame exclusive scan
+ *   emit       the same walk writes the codes at the segment's bit offset into the zeroed unstuffed stream
+ *   stuffing   FF bytes counted per 64-byte chunk, the counts scanned per frame (that launch also writes the header, the
+ *              EOI and the frame's result row), then the chunks scattered behind the header with the 00 bytes inserted
+ *   frames     device, uint8 [B][h][w][3] contiguous
+ *   tables     the struct t3d_jpeg_encode_setup filled, in HOST memory: the call reads the geometry from it (grid sizes and the
+ *              argument checks need it without a read-back); tables_dev: a copy of the same struct in DEVICE memory, from
+ *              which the kernels read the divisors, the code tables and the header.  Every index and range the kernels use
+ *              comes from the host copy, so memory safety does not depend on the device copy.
+ *   out        device, frame i's file at out + i * cap_bytes; results [B] device: bytes = the file's length, overflow = 0; or,
+ *              when the file does not fit cap_bytes or its unstuffed scan does not fit its share of work (cap_bytes rounded up
+ *              to 64), overflow = 1 and bytes = header + unstuffed scan + 2, a lower bound of the need -- stuffing at most
+ *              doubles the scan, so a slot of 2 * bytes always suffices.  An overflowing frame writes nothing outside its own
+ *              slot and every other frame of the call is unaffected.
+ *   work       device, 16-byte aligned, t3d_jpeg_encode_work_bytes bytes
+ * T3D_ERR_ARG, nothing launched: a NULL pointer, B < 0 or > 65535, tables not one that setup fills, out or work not 16-byte
+ * aligned, seg_mcus < 1, cap_bytes below header + 2, work_bytes below the query.  B == 0 returns T3D_OK and launches nothing. */
+typedef struct t3d_jpeg_enc_tables {
+  int h, w, quality, sampling;           /* T3D_JPEG_444 / T3D_JPEG_420 */
+  int mcus_x, mcus_y, mcu_blocks, blocks;        /* the MCU grid, 3 or 6 blocks an MCU, blocks of a frame */
+  int luma_rows, luma_cols;              /* ceil(h / 8), ceil(w / 8): luma blocks beyond them are dummies (4:2:0) */
+  int header_bytes, reserved;
+  unsigned short divisor[2][64];         /* 8 * quantisation entry, natural (row-major) order; luminance, chrominance */
+  unsigned int huff[4][256];             /* DC 0, DC 1, AC 0, AC 1 by symbol: code length << 16 | code; 0: no such symbol */
+  unsigned char header[640];             /* SOI .. SOS, header_bytes of them */
+} t3d_jpeg_enc_tables;
+typedef struct t3d_jpeg_enc_result {
+  long long bytes;
+  int overflow, reserved;
+} t3d_jpeg_enc_result;
+int t3d_jpeg_encode_setup(int h, int w, int quality, int sampling, t3d_jpeg_enc_tables* out);
+int t3d_jpeg_encode_work_bytes(int B, int h, int w, int sampling, int seg_mcus, long long cap_bytes, long long* bytes);
+int t3d_jpeg_encode_u8(const unsigned char* frames, int B, const t3d_jpeg_enc_tables* tables,
+                       const t3d_jpeg_enc_tables* tables_dev, int seg_mcus, unsigned char* out, long long cap_bytes,
+                       t3d_jpeg_enc_result* results, void* work, long long work_bytes, void* stream);
+
 /* Materialise a block output:  z = act(scale*y + shift) + residual   (residual may be NULL; scale NULL = identity).
  * Replaces the BatchNorm normalise pass + `x + self.conv(x)` (mobilenetv3.py:159,162-164). y,z,residual [M,C]. */
 int t3d_bn_apply(int dtype, const void* y, const t3d_prologue* pro, const void* residual, void* z, int M, int C,
