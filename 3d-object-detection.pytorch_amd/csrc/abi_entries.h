@@ -37,7 +37,8 @@
   Q(t3d_pwconv_bwd_yfree_scratch) Q(t3d_dwconv_route) Q(t3d_dwconv_force_route) \
   Q(t3d_augment_crops_u8) Q(t3d_augment_resized_u8) Q(t3d_augment_chain_crops_u8) Q(t3d_augment_chain_resized_u8) \
   Q(t3d_detect_augment_u8) Q(t3d_detect_draw) Q(t3d_detect_draw_host) Q(t3d_jpeg_index) Q(t3d_jpeg_decode_work_bytes) Q(t3d_jpeg_decode_u8) Q(t3d_jpeg_decode_roi_u8) \
-  Q(t3d_jpeg_encode_setup) Q(t3d_jpeg_encode_work_bytes) Q(t3d_jpeg_encode_u8) \
+  Q(t3d_jpeg_header) Q(t3d_jpeg_index_work_bytes) Q(t3d_jpeg_index_device) \
+  Q(t3d_jpeg_encode_setup)Q(t3d_jpeg_encode_work_bytes) Q(t3d_jpeg_encode_u8) \
   Q(t3d_ssd_multibox_work_bytes) Q(t3d_ssd_head_bwd_work_bytes) Q(t3d_track_state_bytes) Q(t3d_track_lds_bytes) \
   Q(t3d_draw_glyphs) Q(t3d_set_launch_events) Q(t3d_fold_pending) Q(t3d_expdw_supported) \
   Q(t3d_plan_create) Q(t3d_plan_destroy) Q(t3d_plan_add_call) Q(t3d_plan_add_fork) Q(t3d_plan_add_fork_after) \

@@ -1,6 +1,8 @@
 // The host half of the device JPEG decode (include/t3d.h, next to t3d_jpeg_index): parse the markers of a baseline file, walk
 // its one entropy-coded scan and record where every seg_mcus-th MCU starts.  No HIP include and no allocation: a stand-alone
 // host program compiles this header on its own (tools/jpeg_index_check.cpp runs it under the sanitizers).
+// The two halves are two functions: the markers (t3d_jpeg_markers_impl; t3d_jpeg_header is it plus the table check, for files whose
+// scan the device walks: csrc/jpeg_scan.h) and the scan walk, which t3d_jpeg_index_impl runs behind the markers.
 // What the device decoder shares with it -- the Huffman table expansion and the zig-zag order -- is marked T3D_JPEG_HD.
 #pragma once
 #include <stdint.h>
@@ -138,11 +140,12 @@ inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
 }  // namespace t3d_jpeg_host
 
-// include/t3d.h: t3d_jpeg_index
-inline int t3d_jpeg_index_impl(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info, t3d_jpeg_seg* segs,
-                               long long seg_capacity) {
+// The MARKER half of the indexer: everything of *info but scan_bytes (left 0), from the markers up to and including SOS.  Nothing
+// of the scan is read.  have_dc / have_ac: which Huffman tables the file defined.
+inline int t3d_jpeg_markers_impl(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info, bool have_dc[2],
+                                 bool have_ac[2]) {
   using namespace t3d_jpeg_host;
-  if (!data || !info || bytes < 0 || seg_mcus < 1 || (segs && seg_capacity < 0)) return T3D_ERR_ARG;
+  if (!data || !info || bytes < 0 || seg_mcus < 1) return T3D_ERR_ARG;
   memset(info, 0, sizeof(*info));
   info->seg_mcus = seg_mcus;
   auto unsupported = [&](int reason) {
@@ -152,7 +155,8 @@ inline int t3d_jpeg_index_impl(const unsigned char* data, long long bytes, int s
   if (bytes < 4 || data[0] != 0xFF || data[1] != 0xD8) return T3D_ERR_ARG;
   static const uint8_t zigzag[64] = T3D_JPEG_ZIGZAG;
   uint8_t qt[4][64];
-  bool have_q[4] = {false, false, false, false}, have_dc[2] = {false, false}, have_ac[2] = {false, false};
+  bool have_q[4] = {false, false, false, false};
+  have_dc[0] = have_dc[1] = have_ac[0] = have_ac[1] = false;
   bool have_sof = false;
   int comp_id[3] = {0, 0, 0}, comp_h[3] = {0, 0, 0}, comp_v[3] = {0, 0, 0}, comp_tq[3] = {0, 0, 0};
   int adobe_transform = -1;
@@ -249,7 +253,6 @@ inline int t3d_jpeg_index_impl(const unsigned char* data, long long bytes, int s
     pos += len;
   }
 
-  // ---- the scan ----
   const int mcu_px = info->sampling == T3D_JPEG_420 ? 16 : 8;
   info->mcus_x = (info->w + mcu_px - 1) / mcu_px, info->mcus_y = (info->h + mcu_px - 1) / mcu_px;
   const long long nmcu = (long long)info->mcus_x * info->mcus_y;
@@ -258,12 +261,48 @@ inline int t3d_jpeg_index_impl(const unsigned char* data, long long bytes, int s
   info->nseg = (int)nseg;
   info->scan_offset = pos;
   if (bytes - pos > 0xFFFFFFFFll) return T3D_ERR_ARG;      // (t3d_jpeg_seg.byte is 32 bits)
-  if (segs && seg_capacity < nseg) return T3D_ERR_ARG;
-  t3d_jpeg_huff dc[2], ac[2];
+  return T3D_OK;
+}
+
+// the file's Huffman tables expanded -> false: one of them is no prefix code
+inline bool t3d_jpeg_file_tables(const t3d_jpeg_info* info, const bool have_dc[2], const bool have_ac[2], t3d_jpeg_huff dc[2],
+                                 t3d_jpeg_huff ac[2]) {
   for (int t = 0; t < 2; ++t) {
-    if (have_dc[t] && !t3d_jpeg_build_huff(info->dc_bits[t], info->dc_vals[t], 16, &dc[t])) return T3D_ERR_ARG;
-    if (have_ac[t] && !t3d_jpeg_build_huff(info->ac_bits[t], info->ac_vals[t], 256, &ac[t])) return T3D_ERR_ARG;
+    if (have_dc[t] && !t3d_jpeg_build_huff(info->dc_bits[t], info->dc_vals[t], 16, &dc[t])) return false;
+    if (have_ac[t] && !t3d_jpeg_build_huff(info->ac_bits[t], info->ac_vals[t], 256, &ac[t])) return false;
   }
+  return true;
+}
+
+// include/t3d.h: t3d_jpeg_header
+inline int t3d_jpeg_header_impl(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info) {
+  bool have_dc[2], have_ac[2];
+  const int rc = t3d_jpeg_markers_impl(data, bytes, seg_mcus, info, have_dc, have_ac);
+  if (rc != T3D_OK) return rc;
+  t3d_jpeg_huff dc[2], ac[2];
+  if (!t3d_jpeg_file_tables(info, have_dc, have_ac, dc, ac)) return T3D_ERR_ARG;
+  info->scan_bytes = bytes - info->scan_offset;            // the clamp: the scan's length is the scan walk's to find
+  return T3D_OK;
+}
+
+// include/t3d.h: t3d_jpeg_index
+inline int t3d_jpeg_index_impl(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info, t3d_jpeg_seg* segs,
+                               long long seg_capacity) {
+  using namespace t3d_jpeg_host;
+  if (segs && seg_capacity < 0) return T3D_ERR_ARG;
+  bool have_dc[2], have_ac[2];
+  const int rc = t3d_jpeg_markers_impl(data, bytes, seg_mcus, info, have_dc, have_ac);
+  if (rc != T3D_OK) return rc;
+  auto unsupported = [&](int reason) {
+    info->reason = reason;
+    return (int)T3D_ERR_UNSUPPORTED;
+  };
+  // ---- the scan ----
+  const long long pos = info->scan_offset;
+  const long long nmcu = (long long)info->mcus_x * info->mcus_y;
+  if (segs && seg_capacity < info->nseg) return T3D_ERR_ARG;
+  t3d_jpeg_huff dc[2], ac[2];
+  if (!t3d_jpeg_file_tables(info, have_dc, have_ac, dc, ac)) return T3D_ERR_ARG;
   Bits br;
   br.init(data + pos, bytes - pos);
   int pred[3] = {0, 0, 0};

@@ -17,7 +17,12 @@ of the file those segments lie in; only that byte span has to be read and upload
 (`launch_decode_roi`, `decode_jpeg_rois`) writes the packed crops `collate_crops` packs from host-decoded frames.
 
 `decode_jpeg_batch(files, rows)` is the one-call form: a list of file contents and their index rows -> the packed device
-buffer and its descriptor table, the layout `collate_frames` produces."""
+buffer and its descriptor table, the layout `collate_frames` produces.
+
+A frame nobody has indexed -- a video or camera frame -- needs no host walk: `read_jpeg_header` reads its markers,
+`index_jpeg_device` builds the index rows of a batch on the device (`t3d_jpeg_index_device`: the host indexer's rows, byte for
+byte), `decode_jpeg_frames(files)` chains the decode behind it with nothing read back, and `JpegIndex.build(where='device')`
+builds a saved index that way."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -25,7 +30,8 @@ import numpy as np
 
 __all__ = ['JpegIndex', 'decode_jpeg_batch', 'index_jpeg', 'collate_jpeg', 'INFO_DTYPE', 'SEG_DTYPE', 'ITEM_DTYPE',
            'DEFAULT_SEG_MCUS', 'REASONS', 'roi_mcus', 'plan_roi', 'plan_roi_batch', 'launch_decode_roi', 'decode_jpeg_rois',
-           'ROI_SEG_MCUS', 'ROI_READ_AHEAD']
+           'ROI_SEG_MCUS', 'ROI_READ_AHEAD', 'read_jpeg_header', 'index_jpeg_device', 'decode_jpeg_frames', 'DEFAULT_SUB_BYTES',
+           'SUB_BYTES_RANGE']
 
 # include/t3d.h: t3d_jpeg_info (864 bytes), t3d_jpeg_seg (16), t3d_jpeg_item (48)
 INFO_DTYPE = np.dtype([('h', '<i4'), ('w', '<i4'), ('ncomp', '<i4'), ('sampling', '<i4'), ('mcus_x', '<i4'), ('mcus_y', '<i4'),
@@ -48,6 +54,11 @@ REASONS = {0: 'decoded on the device', 1: 'not a baseline frame (progressive, ex
 ROI_SEG_MCUS = 1
 # bytes uploaded behind the byte the segment after the last needed one begins in: the device's 64-bit window reads ahead
 ROI_READ_AHEAD = 8
+# raw bytes of the stuffed scan per lane of the device indexer (include/t3d.h: t3d_jpeg_index_device).  tools/time_jpeg_index.py
+# sweeps 4 .. 512: the best of the sweep at 80 frames of 1440 x 1920 (and at 1 and 8 of 1080 x 1920)
+DEFAULT_SUB_BYTES = 512
+SUB_BYTES_RANGE = (4, 1 << 30)
+_INDEX_BATCH = 64                       # files per device call of JpegIndex.build(where='device')
 _BLOCKS_PER_MCU = (1, 3, 6)             # gray, 4:4:4, 4:2:0
 _MAGIC = 0x7833644A50454731             # 'x3dJPEG1'
 
@@ -65,6 +76,16 @@ def index_jpeg(data, seg_mcus=DEFAULT_SEG_MCUS):
     return rc, info[0], segs
 
 
+def read_jpeg_header(data, seg_mcus=DEFAULT_SEG_MCUS):
+    """One file's bytes -> (return code of t3d_jpeg_header, info record): the markers only, nothing of the scan; the record is
+    `index_jpeg`'s except that scan_bytes is the bytes from scan_offset to the file's end.  Host only: no GPU is touched."""
+    from .. import _native as N
+    a = np.frombuffer(data, np.uint8)
+    info = np.zeros(1, INFO_DTYPE)
+    rc = N.lib().t3d_jpeg_header(a.ctypes.data, a.size, int(seg_mcus), info.ctypes.data)
+    return rc, info[0]
+
+
 class JpegIndex:
     """The index of a list of files, as flat numpy arrays: `infos` [n] INFO_DTYPE, `segs` [total] SEG_DTYPE, `seg_start` int64
     [n + 1] (file i owns segs[seg_start[i]:seg_start[i + 1]]), `size` and `mtime_ns` int64 [n] of the file when it was indexed,
@@ -78,11 +99,17 @@ class JpegIndex:
         return len(self.files)
 
     @classmethod
-    def build(cls, files, root, seg_mcus=DEFAULT_SEG_MCUS, threads=8):
-        """Index `files` (names relative to `root`) with `threads` <= 16 host threads of THIS process."""
+    def build(cls, files, root, seg_mcus=DEFAULT_SEG_MCUS, threads=8, where='host'):
+        """Index `files` (names relative to `root`) with `threads` <= 16 host threads of THIS process.  where='device': the
+        threads read the files and their markers, the scans are walked on the device in batches (`index_jpeg_device`) and the
+        rows read back; a file the device refuses goes through the host indexer, so every array equals the host build's."""
         from .. import _native as N
         N.lib()                                     # (load it once, before the threads ask for it)
         threads = max(1, min(int(threads), 16))
+        if where not in ('host', 'device'):
+            raise ValueError(f"where={where!r}: 'host' or 'device'")
+        if where == 'device':
+            return cls._build_device(files, root, seg_mcus, threads)
 
         def one(name):
             path = os.path.join(str(root), name)
@@ -92,6 +119,48 @@ class JpegIndex:
             return info, segs, st.st_size, st.st_mtime_ns, reason
         with ThreadPoolExecutor(max_workers=threads) as ex:
             rows = list(ex.map(one, files))
+        infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
+        seg_start = np.concatenate([[0], np.cumsum([len(r[1]) for r in rows])]).astype(np.int64)
+        segs = np.concatenate([r[1] for r in rows] + [np.zeros(0, SEG_DTYPE)])
+        return cls(files, infos, segs, seg_start, np.array([r[2] for r in rows], np.int64), np.array([r[3] for r in rows], np.int64),
+                   np.array([r[4] for r in rows], np.int64), seg_mcus)
+
+    @classmethod
+    def _build_device(cls, files, root, seg_mcus, threads):
+        import torch
+
+        from .. import _native as N
+        if not torch.cuda.is_available():
+            raise RuntimeError("JpegIndex.build(where='device') needs a GPU and none is present: build with where='host'")
+
+        def read(name):
+            path = os.path.join(str(root), name)
+            st = os.stat(path)
+            data = np.fromfile(path, np.uint8)
+            rc, info = read_jpeg_header(data, seg_mcus)
+            return data, rc, info, st.st_size, st.st_mtime_ns
+        rows = []
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            for b0 in range(0, len(files), _INDEX_BATCH):
+                batch = list(ex.map(read, files[b0:b0 + _INDEX_BATCH]))
+                good = [k for k, r in enumerate(batch) if r[1] == 0]
+                done = {}
+                if good:
+                    infos, segs, seg_start, status = index_jpeg_device([batch[k][0] for k in good], seg_mcus)
+                    infos = infos.cpu().numpy().view(INFO_DTYPE)
+                    segs, status = segs.cpu().numpy().view(SEG_DTYPE), status.cpu().numpy()
+                    for n, k in enumerate(good):
+                        if status[n] == 0:
+                            done[k] = (infos[n].copy(), segs[seg_start[n]:seg_start[n + 1]].copy(), 0)
+                for k, (data, rc, info, size, mtime) in enumerate(batch):
+                    if k in done:
+                        info, segs, reason = done[k]
+                    elif rc == 0:                       # the device refuses its scan: the host indexer says why, in its own words
+                        rc, info, segs = index_jpeg(data, seg_mcus)
+                        reason = 0 if rc == 0 else (int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1)
+                    else:
+                        segs, reason = np.zeros(0, SEG_DTYPE), int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1
+                    rows.append((info, segs, size, mtime, reason))
         infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
         seg_start = np.concatenate([[0], np.cumsum([len(r[1]) for r in rows])]).astype(np.int64)
         segs = np.concatenate([r[1] for r in rows] + [np.zeros(0, SEG_DTYPE)])
@@ -260,6 +329,89 @@ def decode_jpeg_batch(files, rows, device=None):
 
 
 decode_jpeg_batch.last_status = None
+
+
+# ---- the index built on the device: t3d_jpeg_index_device -------------------------------------------------------------------------
+def _index_device(files, seg_mcus, sub_bytes, device, decode=False):
+    """Headers on the host, ONE upload, ONE t3d_jpeg_index_device call on the current stream.  -> dict(data, infos, segs, items
+    (device uint8 tensors; items: the DECODE's table when `decode`), status (device int32 [B]), seg_start (host int64 [B + 1]),
+    heads (the host's header records), plan (what `launch_decode` takes), work (the call's workspace, settle rounds included))."""
+    import ctypes
+
+    import torch
+
+    from .. import _native as N
+    lo, hi = SUB_BYTES_RANGE
+    sub_bytes = int(sub_bytes)
+    if not lo <= sub_bytes <= hi:
+        raise ValueError(f'sub_bytes={sub_bytes}: {lo} .. {hi}')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    arrs = [np.frombuffer(f, np.uint8) for f in files]
+    heads = np.zeros(len(arrs), INFO_DTYPE)
+    for i, a in enumerate(arrs):
+        rc, heads[i] = read_jpeg_header(a, seg_mcus)
+        if rc != 0:
+            raise ValueError(f'file {i} of the batch is not decoded on the device: '
+                             f'{REASONS[int(heads[i]["reason"]) if rc == N.ERR_UNSUPPORTED else -1]}')
+    B = len(arrs)
+    sizes = np.array([a.size for a in arrs], np.int64)
+    nseg = heads['nseg'].astype(np.int64)
+    seg_start = np.concatenate([[0], np.cumsum(nseg)]).astype(np.int64)
+    status = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+    if B == 0:
+        empty = torch.empty(0, dtype=torch.uint8, device=dev)
+        return dict(data=empty, infos=empty, segs=empty, items=empty, status=status[:0], seg_start=seg_start, heads=heads, plan=None,
+                    work=empty)
+    nsub = -(-heads['scan_bytes'].astype(np.int64) // sub_bytes)
+    blocks = heads['mcus_x'].astype(np.int64) * heads['mcus_y'] * np.asarray(_BLOCKS_PER_MCU, np.int64)[heads['sampling']]
+    items = np.zeros(B, ITEM_DTYPE)
+    items['file_offset'], items['file_bytes'] = np.cumsum(sizes) - sizes, sizes
+    items['seg_offset'], items['block_offset'] = seg_start[:-1], np.cumsum(nsub) - nsub      # block_offset: subsequence records
+    parts = [np.concatenate(arrs), heads.view(np.uint8), items.view(np.uint8)]
+    if decode:
+        ditems = items.copy()
+        nb = heads['h'].astype(np.int64) * heads['w'] * 3
+        ditems['out_offset'], ditems['block_offset'] = np.cumsum(nb) - nb, np.cumsum(blocks) - blocks
+        parts.append(ditems.view(np.uint8))
+    parts = _upload_parts(parts, dev)
+    total_segs = int(seg_start[-1])
+    segs = torch.empty(total_segs * SEG_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    nbytes = ctypes.c_longlong(0)
+    if N.lib().t3d_jpeg_index_work_bytes(int(heads['scan_bytes'].sum()), B, sub_bytes, ctypes.byref(nbytes)) != 0:
+        raise RuntimeError('t3d_jpeg_index_work_bytes failed')
+    work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+    N.call('t3d_jpeg_index_device', N.ptr(parts[0]), parts[0].numel(), N.ptr(parts[1]), N.ptr(segs), total_segs, N.ptr(parts[2]), sub_bytes,
+           N.ptr(work), work.numel(), N.ptr(status), B, int(nsub.max()), N.stream())
+    plan = dict(infos=heads, total_segs=total_segs, total_blocks=int(blocks.sum()), max_segs=int(nseg.max()), max_blocks=int(blocks.max()))
+    return dict(data=parts[0], infos=parts[1], segs=segs, items=parts[-1], status=status[:B], seg_start=seg_start, heads=heads, plan=plan,
+                work=work)
+
+
+def index_jpeg_device(files, seg_mcus=DEFAULT_SEG_MCUS, sub_bytes=DEFAULT_SUB_BYTES, device=None):
+    """files: the contents of B JPEG files nobody has indexed -> (infos, segs, seg_start, status): the index rows built on the
+    device.  infos: device uint8 [B * 864] (INFO_DTYPE records), segs: device uint8 [total * 16] (SEG_DTYPE rows), file i's from
+    seg_start[i] (host int64 [B + 1]) on, status: device int32 [B] -- 0: the rows and scan_bytes are `index_jpeg`'s, byte for
+    byte; 1: a scan the host indexer calls malformed (its scan_bytes is -1: a decode given the record refuses the image).
+    The markers are read on the host; then one upload and one t3d_jpeg_index_device call on the current stream, nothing is read
+    back.  ValueError: a file whose markers the device path does not take, naming its reason from REASONS."""
+    d = _index_device(files, seg_mcus, sub_bytes, device)
+    return d['infos'], d['segs'], d['seg_start'], d['status']
+
+
+def decode_jpeg_frames(files, device=None, seg_mcus=DEFAULT_SEG_MCUS, sub_bytes=DEFAULT_SUB_BYTES):
+    """files: the contents of B JPEG files nobody has indexed -> (packed device uint8 [sum h * w * 3], desc int64 [B, 3] =
+    (offset, h, w)), the layout of `decode_jpeg_batch`.  t3d_jpeg_index_device and t3d_jpeg_decode_u8 back to back on the
+    current stream: no host scan walk, nothing read back.  `decode_jpeg_frames.last_status` = (the indexer's, the decode's)
+    device status vectors: a frame whose scan the indexer refuses (1) is refused by the decode (2) and its pixels are not written."""
+    d = _index_device(files, seg_mcus, sub_bytes, device, decode=True)
+    out, desc = _packed([(int(h['h']), int(h['w'])) for h in d['heads']], d['status'].device)
+    if not len(files):
+        return out, desc
+    decode_jpeg_frames.last_status = (d['status'], launch_decode(d['data'], d['infos'], d['segs'], d['items'], d['plan'], out))
+    return out, desc
+
+
+decode_jpeg_frames.last_status = None
 
 
 # ---- one pixel rectangle per file: t3d_jpeg_decode_roi_u8 ---------------------------------------------------------------------

@@ -193,6 +193,23 @@ class MjpegReader:
     def __iter__(self):
         return (self[i] for i in range(len(self.frames)))
 
+    def frames_device(self, start, count, device=None):
+        """Frames start .. start + count - 1 decoded on the device -> (uint8 [count, H, W, 3], (index status, decode status)): the
+        tensor `FramePipeline.process_device` takes, and the two device int32 [count] status vectors of
+        `decode_jpeg_frames` (0, 0: decoded).  No host scan walk, nothing read back.  For chunks that are baseline files of the
+        stream's size; ValueError for a chunk whose markers the device path does not take or whose size is another (the caller
+        has Pillow for those)."""
+        from ..dataloaders import jpeg as J
+        start, count = int(start), int(count)
+        if count < 1 or start < 0 or start + count > len(self.frames):
+            raise ValueError(f'frames {start} .. {start + count - 1} of {len(self.frames)}')
+        files = [self[i] for i in range(start, start + count)]
+        packed, desc = J.decode_jpeg_frames(files, device)
+        W, H = self.size
+        if not (desc[:, 1] == H).all() or not (desc[:, 2] == W).all():
+            raise ValueError(f'a chunk is not {H} x {W}, the size the stream header states')
+        return packed.view(count, H, W, 3), J.decode_jpeg_frames.last_status
+
     def close(self):
         if self.f is not None:
             self.f.close()

@@ -581,6 +581,60 @@ int t3d_jpeg_decode_roi_u8(const unsigned char* data, long long data_bytes, cons
                            long long out_bytes, void* work, long long work_bytes, long long total_blocks, int* status, int B,
                            long long max_lanes, int max_blocks, long long max_runs, void* stream);
 
+/* The MCU index BUILT ON THE DEVICE (csrc/jpeg_scan.h, csrc/jpeg_scan.hip): for a frame nobody has indexed -- a video or camera
+ * frame -- the host reads only the markers (t3d_jpeg_header) and the device finds the MCU starts and DC predictors of every
+ * frame of a batch (t3d_jpeg_index_device).  The rows are t3d_jpeg_index's, byte for byte; t3d_jpeg_decode_u8 runs behind it
+ * unchanged.
+ *
+ * t3d_jpeg_header (HOST ONLY like t3d_jpeg_index: no HIP call; every read is checked against `bytes`): the marker half of
+ * t3d_jpeg_index and nothing of the scan.  The same return codes and the same info->reason for every file the markers refuse
+ * (a Huffman table that is no prefix code included); *info as t3d_jpeg_index fills it, except that scan_bytes is the bytes from
+ * scan_offset to the end of the file -- the clamp of every scan read, not yet the scan's length.
+ *
+ * DEFINITION of t3d_jpeg_index_device: infos[i].scan_bytes and image i's nseg rows of segs are what t3d_jpeg_index writes for
+ * file i and infos[i].seg_mcus, `reserved` included, and status[i] == 0, exactly when t3d_jpeg_index returns T3D_OK for it.
+ * METHOD.  Baseline Huffman streams self-synchronise.  The stuffed scan is cut into subsequences of sub_bytes raw bytes, one
+ * lane each; a lane owns every symbol (a code plus its extra bits) whose first bit lies in its subsequence.  The state that
+ * crosses a boundary: the next symbol's byte and bit (the convention of t3d_jpeg_seg), the block slot in the MCU, the next
+ * zig-zag position, or "no valid state".  speculate: every lane decodes from its first byte as if an MCU began there (lane 0's
+ * entry is true).  settle: every lane takes its predecessor's exit as its entry and decodes again where that changed, until no
+ * lane changed -- then the chain is the sequential decode; at most nsub rounds whatever the data, only the time depends on how
+ * fast the stream synchronises.  count: an exclusive scan per image of the MCU starts and the DC differences per component.
+ * emit: every lane decodes once more with its true entry, MCU number and predictors, writes the rows of the MCUs it owns and
+ * applies the host indexer's checks to everything before the end of the last MCU; the lane in which the last MCU ends checks
+ * the trailer (the rest of the byte, fill FFs, FF D9).  What lies behind that point is never trusted.
+ * FOUR kernels on `stream` whatever B is (speculate; settle + count, one workgroup per image, rounds separated by workgroup
+ * barriers; emit; finish), no memset, no allocation, no host synchronisation, no read-back.  No workgroup waits for another.
+ *   data [data_bytes]      the files' bytes, image i at items[i].file_offset, file_bytes long
+ *   infos [B]  IN and OUT  as t3d_jpeg_header filled them.  scan_bytes is not read: the clamp is file_bytes - scan_offset.
+ *                          On return scan_bytes is the scan's length (status 0) or -1 (status 1 or 2): t3d_jpeg_decode_u8
+ *                          given these infos refuses such an image with its own status 2
+ *   segs [total_segs] OUT  image i's nseg rows from items[i].seg_offset on; rows of an image with status 1 are unspecified
+ *   items [B]              t3d_jpeg_item read this way: file_offset, file_bytes, seg_offset as for t3d_jpeg_decode_u8;
+ *                          block_offset: the image's first SUBSEQUENCE RECORD in work (in records, not blocks), it owns
+ *                          nsub = ceil((file_bytes - scan_offset) / sub_bytes) of them; out_offset and reserved are not read
+ *   sub_bytes              4 .. 2^30 raw bytes of the stuffed scan a lane
+ *   work [work_bytes]      t3d_jpeg_index_work_bytes(sum of the images' file_bytes - scan_offset, B, sub_bytes) bytes, 16-byte
+ *                          aligned: B records of 32 bytes (one an image), then 32 bytes a subsequence
+ *   status int32 [B] OUT   0: indexed.  1: a scan t3d_jpeg_index returns T3D_ERR_ARG for (no such code, a DC category above 11,
+ *                          a run past coefficient 63, a predictor outside int16, a marker or the end of the data inside the
+ *                          scan, no EOI behind it; a second scan, which t3d_jpeg_index calls unsupported, lands here too).
+ *                          2: the record is inconsistent (an info the header would not write, a table that is no prefix code, a
+ *                          range outside data / segs / work) -- nothing of that image's bytes, rows or records is read or
+ *                          written
+ *   max_subs               an upper bound of one image's nsub: it sizes the grids; the kernels loop, so a bound that is too
+ *                          small costs time, not correctness
+ * Memory safety does not depend on the stream: every read of it is clamped to the image's bytes, a decode step consumes at least
+ * one bit or ends the lane, a lane ends at its subsequence's end, every row and record index is checked against the image's share.
+ * T3D_ERR_ARG, nothing launched: a NULL pointer, B < 0 or > 65535, sub_bytes outside 4 .. 2^30, data_bytes or total_segs <= 0,
+ * max_subs < 1, work misaligned or work_bytes below 32 * B.  B == 0 returns T3D_OK and launches nothing.
+ * t3d_jpeg_index_work_bytes: T3D_ERR_ARG for bytes NULL, a negative total, B < 0 or > 65535, sub_bytes outside its range. */
+int t3d_jpeg_header(const unsigned char* data, long long bytes, int seg_mcus, t3d_jpeg_info* info);
+int t3d_jpeg_index_work_bytes(long long total_scan_bytes, int B, int sub_bytes, long long* bytes);
+int t3d_jpeg_index_device(const unsigned char* data, long long data_bytes, t3d_jpeg_info* infos, t3d_jpeg_seg* segs,
+                          long long total_segs, const t3d_jpeg_item* items, int sub_bytes, void* work, long long work_bytes,
+                          int* status, int B, int max_subs, void* stream);
+
 /* Baseline JPEG ENCODE on the device (csrc/jpeg_encode.h, csrc/jpeg_encode.hip): B RGB uint8 frames [B][h][w][3] of one size ->
  * B baseline JFIF files, the third leg beside t3d_jpeg_index and t3d_jpeg_decode_u8 (the files carry no restart markers: the
  * index accepts them with reason 0).  torchdet3d/utils/jpeg_encode.py wraps it, torchdet3d/utils/mjpeg.py puts the files into
