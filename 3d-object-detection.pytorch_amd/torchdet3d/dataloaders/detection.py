@@ -31,7 +31,7 @@ from PIL import Image
 
 from ..utils import OBJECTRON_CLASSES
 
-__all__ = ['ObjectronFrames', 'DetectionAugmentPipeline', 'collate_frames', 'DET_SAMPLE_DTYPE']
+__all__ = ['ObjectronFrames', 'DetectionAugmentPipeline', 'collate_frames', 'resize_boxes', 'DET_SAMPLE_DTYPE']
 
 # include/t3d.h: t3d_det_sample (80 bytes) and its flags
 DET_SAMPLE_DTYPE = np.dtype([('offset', '<i8'), ('h', '<i4'), ('w', '<i4'), ('turns', '<i4'), ('left', '<i4'), ('top', '<i4'),
@@ -160,6 +160,14 @@ def collate_frames(items):
     counts = np.asarray([len(l) for _, _, l in items], np.int64)
     return (torch.from_numpy(packed), torch.from_numpy(desc), torch.from_numpy(boxes), torch.from_numpy(labels),
             torch.from_numpy(counts))
+
+
+def resize_boxes(boxes, row, h, w, size):
+    """mmdet's Resize of the boxes of a batch, scale then clip to the image: boxes float32 [n, 4], row [n] the image each
+    belongs to, h and w int64 [B] of the frames, size (oh, ow) of the output.  -> float32 [n, 4]."""
+    oh, ow = size
+    sc = np.stack([ow / w, oh / h, ow / w, oh / h], 1).astype(np.float32)
+    return np.minimum(np.maximum(boxes * sc[row], np.float32(0)), np.array([ow, oh, ow, oh], np.float32))
 
 
 # the order the kernel applies the steps in: the config's

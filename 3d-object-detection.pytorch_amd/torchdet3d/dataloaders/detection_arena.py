@@ -23,16 +23,19 @@ the same route without the draw: records with no flag, `t3d_augment_crops_u8`, b
 
 Yields what `GpuDetectionLoader` yields, bit for bit, with ONE difference: G, the second dimension of `gt_boxes` and
 `gt_labels`, is the ARENA's capacity -- the largest box count of any image of the set, at least 1 -- not the batch's largest
-count.  Rows past a count are zero and every consumer reads `gt_counts`.  `prefetch`, the copy stream, the ready event,
-`record_stream`, `sampler`, `__len__`, `last_status`, `dataset` and `batch_size` are `GpuDetectionLoader`'s."""
-import collections
+count.  Rows past a count are zero and every consumer reads `gt_counts`.  The pinned staging of the fill and of the batches,
+the packed upload, `prefetch`, the copy stream and the hand-over to the consumer are staging.py's; `sampler`, `__len__`,
+`last_status`, `dataset` and `batch_size` mean what they mean on `GpuDetectionLoader`."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+import torch
 
-from .detection import DET_SAMPLE_DTYPE, _CROP_TAG
-from .jpeg import _BLOCKS_PER_MCU, ITEM_DTYPE
+from .detection import DET_SAMPLE_DTYPE, _CROP_TAG, resize_boxes
+from .jpeg import frame_blocks, item_table, launch_decode, starts
+from .objectron import resize_records
+from .staging import PinnedRing, StagedLoader, device_parts, upload
 
 __all__ = ['DetectionArena', 'ArenaDetectionLoader', 'plan_arena_batch', 'pipeline_cfg', 'key_words', 'detect_draw_host',
            'DRAW_CFG_LEN', 'MAX_BOXES']
@@ -113,9 +116,7 @@ def plan_arena_batch(idx, file_off, size, seg_start, h, w, blocks, nseg):
     hh, ww = h[idx].astype(np.int64), w[idx].astype(np.int64)
     nb = hh * ww * 3
     bl = blocks[idx].astype(np.int64)
-    items = np.zeros(len(idx), ITEM_DTYPE)
-    items['file_offset'], items['file_bytes'], items['seg_offset'] = file_off[idx], size[idx], seg_start[idx]
-    items['out_offset'], items['block_offset'] = np.cumsum(nb) - nb, np.cumsum(bl) - bl
+    items = item_table(file_off[idx], size[idx], starts(nb), seg_start[idx], bl)
     frames = np.stack([items['out_offset'], hh, ww, idx], 1) if len(idx) else np.zeros((0, 4), np.int64)
     return dict(items=items, frames=frames, out_bytes=int(nb.sum()), total_blocks=int(bl.sum()),
                 max_segs=int(nseg[idx].max()) if len(idx) else 1, max_blocks=int(bl.max()) if len(idx) else 1)
@@ -127,7 +128,6 @@ class DetectionArena:
     fit `max_gb` (GiB, the meaning and default of the regression cache's `data.cache_max_gb`) or an image has more than 64
     boxes -- before anything is allocated.  `fill()` then reads the files and uploads everything."""
     STAGING = 64 << 20          # bytes of one pinned staging buffer (a larger file gets a buffer of its own size)
-    NBUF = 3
 
     def __init__(self, frames, max_gb=32, threads=16):
         if getattr(frames, 'index', None) is None:
@@ -153,8 +153,7 @@ class DetectionArena:
         self.seg_start = np.array(index.seg_start[:-1], np.int64)
         dev = self.kind == 0
         self.nseg = np.where(dev, infos['nseg'], 0).astype(np.int64)
-        self.blocks = np.where(dev, infos['mcus_x'].astype(np.int64) * infos['mcus_y']
-                               * np.asarray(_BLOCKS_PER_MCU, np.int64)[np.clip(infos['sampling'], 0, 2)], 0)
+        self.blocks = np.where(dev, frame_blocks(infos), 0)
         counts = np.array([len(l) for l in fr._labels], np.int64).reshape(-1)
         self.box_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.boxes = np.concatenate([np.asarray(b, np.float32).reshape(-1, 4) for b in fr._boxes] + [np.zeros((0, 4), np.float32)])
@@ -175,7 +174,6 @@ class DetectionArena:
 
     def fill(self, device=None):
         """Read every file (at most 16 threads of this process, rotating pinned staging) and upload the tables.  -> self."""
-        import torch
         if not torch.cuda.is_available():
             raise RuntimeError("data.cache = 'device' keeps the files on the GPU (no CPU fallback)")
         fr, index = self.frames, self.frames.index
@@ -191,7 +189,7 @@ class DetectionArena:
             acc += int(s)
         if len(self.size):
             chunks.append((start, len(self.size)))
-        slots = [[None, None] for _ in range(self.NBUF)]
+        ring = PinnedRing(1)
 
         def read(i, view, base):
             at, n = int(self.file_off[i] - base), int(self.size[i])
@@ -205,18 +203,13 @@ class DetectionArena:
             if got != n or more:
                 raise RuntimeError(f'{path} changed since it was indexed ({n} bytes in the index): rebuild the index')
         with ThreadPoolExecutor(max_workers=self.threads) as ex:
-            for turn, (a, b) in enumerate(chunks):
-                slot = slots[turn % self.NBUF]
+            for a, b in chunks:
                 base, nbytes = int(self.file_off[a]), int(self.size[a:b].sum())
-                if slot[1] is not None:
-                    slot[1].synchronize()          # the upload that last read this buffer has completed
-                if slot[0] is None or slot[0].numel() < nbytes:
-                    slot[0] = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
-                view = slot[0].numpy()
+                slot = ring.take(nbytes)
+                view = slot.host.numpy()
                 list(ex.map(lambda i: read(i, view, base), range(a, b)))
-                self.data[base:base + nbytes].copy_(slot[0][:nbytes], non_blocking=True)
-                slot[1] = torch.cuda.Event()
-                slot[1].record()
+                self.data[base:base + nbytes].copy_(slot.host[:nbytes], non_blocking=True)
+                slot.uploaded(torch.cuda.current_stream(dev))
         self._host_frames = {}
 
         def up(a):
@@ -229,26 +222,23 @@ class DetectionArena:
         return self
 
 
-class ArenaDetectionLoader:
+class ArenaDetectionLoader(StagedLoader):
     """Batches for the detector from a filled `DetectionArena` (the module's docstring): the tuples of `GpuDetectionLoader`, with
     G = `arena.G`.  indices: the dataset indices this loader walks, in order, when there is no sampler (None: all of them);
     `dataset` is what `GpuDetectionLoader.dataset` would be (the frames, or the Subset of them)."""
-    NBUF = 3
 
     def __init__(self, arena, pipeline, batch_size, sampler=None, indices=None, drop_last=False, seed=0, rank=0, prefetch=1,
                  dataset=None):
         if arena.data is None:
             raise RuntimeError('ArenaDetectionLoader needs a filled arena: call DetectionArena.fill() first')
+        super().__init__(prefetch, min_staging=1 << 14)
         self.arena, self.pipeline, self.batch_size = arena, pipeline, int(batch_size)
-        self.seed, self.rank, self.prefetch, self.drop_last = int(seed), int(rank), int(prefetch), bool(drop_last)
+        self.seed, self.rank, self.drop_last = int(seed), int(rank), bool(drop_last)
         self.sampler = sampler
         self.indices = np.arange(len(arena), dtype=np.int64) if indices is None else np.asarray(list(indices), np.int64)
         self.dataset = arena.frames if dataset is None else dataset
         self.decode, self.last_status = 'arena', None
         self._cfg = pipeline_cfg(pipeline)
-        self._slots = [[None, None] for _ in range(self.NBUF)]
-        self._turn = 0
-        self._copy_stream = None
 
     def _order(self):
         return np.fromiter(iter(self.sampler), np.int64) if self.sampler is not None else self.indices
@@ -257,45 +247,31 @@ class ArenaDetectionLoader:
         n = len(self.sampler) if self.sampler is not None else len(self.indices)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
-    def _staging(self, nbytes):
-        import torch
-        slot = self._slots[self._turn]
-        self._turn = (self._turn + 1) % self.NBUF
-        if slot[1] is not None:
-            slot[1].synchronize()
-        if slot[0] is None or slot[0].numel() < nbytes:
-            slot[0] = torch.empty(max(nbytes, 1 << 14), dtype=torch.uint8).pin_memory()
-        return slot
-
     def host_plan(self, idx):
         """The host half of one batch, vectorised numpy only.  idx: the batch's dataset indices.  -> (parts: the uint8 arrays of
         the one upload -- frames | items | gather indices [| records | boxes | labels | counts | shapes for the test pipeline] --
         plan of the device-decoded files, positions of the host-decoded frames)."""
-        from .objectron import AUG_SAMPLE_DTYPE
         A = self.arena
         idx = np.asarray(idx, np.int64)
         B = len(idx)
         hh, ww = A.h[idx], A.w[idx]
         nb = hh * ww * 3
-        out_off = np.cumsum(nb) - nb
+        out_off = starts(nb)
         frames = np.stack([out_off, hh, ww, idx], 1)
         on_dev = np.flatnonzero(A.kind[idx] == 0)
         plan = plan_arena_batch(idx[on_dev], A.file_off, A.size, A.seg_start, A.h, A.w, A.blocks, A.nseg)
         plan['items']['out_offset'] = out_off[on_dev]
-        plan['out_bytes'] = int(nb.sum())
+        plan['out_bytes'], plan['total_segs'] = int(nb.sum()), A.segs.numel() // 16
         parts = [frames.reshape(-1).view(np.uint8), plan['items'].view(np.uint8), idx[on_dev].view(np.uint8)]
         if not self.pipeline.random:
-            oh, ow = self.pipeline.size
             G = A.G
-            rec = np.zeros(B, AUG_SAMPLE_DTYPE)              # flags 0: the resize alone
-            rec['offset'], rec['h'], rec['w'] = out_off, hh, ww
+            rec = resize_records(frames)
             start, cnt = A.box_start[idx], A.box_start[idx + 1] - A.box_start[idx]
             row = np.repeat(np.arange(B), cnt)
             col = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
             src = np.repeat(start, cnt) + col
-            sc = np.stack([ow / ww, oh / hh, ow / ww, oh / hh], 1).astype(np.float32)          # mmdet's Resize: scale, then clip
             gb, gl = np.zeros((B, G, 4), np.float32), np.zeros((B, G), np.int32)
-            gb[row, col] = np.minimum(np.maximum(A.boxes[src] * sc[row], np.float32(0)), np.array([ow, oh, ow, oh], np.float32))
+            gb[row, col] = resize_boxes(A.boxes[src], row, hh, ww, self.pipeline.size)
             gl[row, col] = A.labels[src]
             parts += [rec.view(np.uint8), gb.reshape(-1).view(np.uint8), gl.reshape(-1).view(np.uint8), cnt.astype(np.int32).view(np.uint8),
                       np.stack([hh, ww], 1).astype(np.int32).reshape(-1).view(np.uint8)]
@@ -304,44 +280,26 @@ class ArenaDetectionLoader:
     def finish(self, idx, key_tail, prefetch=None):
         """The batch of dataset indices `idx` -> the device tuple, enqueued on the copy stream (prefetch >= 1: the ready event is
         appended) or on the current stream (prefetch 0)."""
-        import torch
+        return self._public(*self._finish(idx, key_tail, prefetch))
 
+    def _finish(self, idx, key_tail, prefetch=None):
+        """-> (the device tuple, ready event or None)."""
         from .. import _native as N
-        from .jpeg import _launch
         prefetch = self.prefetch if prefetch is None else prefetch
         A = self.arena
         parts, plan, on_host, frames = self.host_plan(idx)
         B, G = len(idx), A.G
         oh, ow = self.pipeline.size
-        offs = np.concatenate([[0], np.cumsum([(p.size + 15) // 16 * 16 for p in parts])])
-        total = int(offs[-1])
-        slot = self._staging(total)
-        host = slot[0]
-        for p, o in zip(parts, offs):
-            host[o:o + p.size].numpy()[...] = p
         dev = A.data.device
-        stream = torch.cuda.current_stream(dev)
-        if prefetch > 0:
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(device=dev)
-            stream = self._copy_stream
+        stream = self._stream(dev, prefetch)
+        part = upload(self._ring, parts, stream, dev).part
         with torch.cuda.stream(stream):
-            meta = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-            meta[:total].copy_(host[:total], non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record(stream)
-
-            def part(k, dtype, *shape):
-                return meta[offs[k]:offs[k] + parts[k].size].view(dtype).view(*shape)
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
             src = torch.empty(max(plan['out_bytes'], 1), dtype=torch.uint8, device=dev)
             n_dev = len(plan['items'])
             if n_dev:
                 infos = A.infos.index_select(0, part(2, torch.int64, n_dev))
-                call = dict(infos=plan['items'], total_segs=A.segs.numel() // 16, total_blocks=plan['total_blocks'],
-                            max_segs=plan['max_segs'], max_blocks=plan['max_blocks'])
-                self.last_status = _launch('t3d_jpeg_decode_u8', A.data, infos, A.segs, (part(1, torch.uint8, -1),), call, src,
-                                           ('max_segs', 'max_blocks'))
+                self.last_status = launch_decode(A.data, infos, A.segs, part(1, torch.uint8, -1), plan, src)
             else:
                 self.last_status = torch.zeros(0, dtype=torch.int32, device=dev)
             for k in on_host:                      # frames the host had to decode (files the index refused) lie in the arena as they are
@@ -350,41 +308,17 @@ class ArenaDetectionLoader:
             if self.pipeline.random:
                 epoch = int(getattr(self.sampler, 'epoch', 0))
                 words = key_words((self.seed, epoch, self.rank) + tuple(key_tail))
-                sizes = [B * 80, B * G * 16, B * G * 4, B * 4, B * 8]
-                o = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])
-                res = torch.empty(int(o[-1]), dtype=torch.uint8, device=dev)
-                rec, gb, gl, gc, diag = (res[o[k]:o[k] + sizes[k]] for k in range(5))
+                rec, gb, gl, gc, diag = device_parts([B * 80, B * G * 16, B * G * 4, B * 4, B * 8], dev)
                 N.call('t3d_detect_draw', self._cfg.ctypes.data, len(self._cfg), words.ctypes.data, len(words), N.ptr(part(0, torch.uint8, -1)),
                        B, N.ptr(A.d_boxes), N.ptr(A.d_labels), N.ptr(A.d_box_start), len(A), len(A.labels), G, N.ptr(rec), N.ptr(gb),
                        N.ptr(gl), N.ptr(gc), N.ptr(diag), N.stream())
                 N.call('t3d_detect_augment_u8', N.ptr(src), src.numel(), N.ptr(rec), N.ptr(imgs), B, oh, ow, N.stream())
-                out = [imgs, gb.view(torch.float32).view(B, G, 4), gl.view(torch.int32).view(B, G), gc.view(torch.int32)]
+                out = (imgs, gb.view(torch.float32).view(B, G, 4), gl.view(torch.int32).view(B, G), gc.view(torch.int32))
             else:
                 N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(part(3, torch.uint8, -1)), N.ptr(imgs), B, oh, ow, N.stream())
-                out = [imgs, part(4, torch.float32, B, G, 4), part(5, torch.int32, B, G), part(6, torch.int32, B), part(7, torch.int32, B, 2)]
-        if prefetch > 0:
-            ready = torch.cuda.Event()
-            ready.record(stream)
-            out.append(ready)
-        return tuple(out)
+                out = (imgs, part(4, torch.float32, B, G, 4), part(5, torch.int32, B, G), part(6, torch.int32, B), part(7, torch.int32, B, 2))
+        return out, self._ready(stream, prefetch)
 
     def __iter__(self):
-        import torch
-        order = self._order()
-        nb = len(self)
-        pending, b = collections.deque(), 0
-        while True:
-            while b < nb and len(pending) <= self.prefetch:
-                pending.append(self.finish(order[b * self.batch_size:(b + 1) * self.batch_size], (b,)))
-                b += 1
-            if not pending:
-                return
-            out = pending.popleft()
-            if self.prefetch > 0:
-                *out, ready = out
-                consumer = torch.cuda.current_stream(out[0].device)
-                consumer.wait_event(ready)
-                for t in out[:2]:                # (boxes, labels, counts and shapes share one allocation)
-                    t.record_stream(consumer)
-                out = tuple(out)
-            yield out
+        order, bs = self._order(), self.batch_size
+        yield from self._batches((order[b * bs:(b + 1) * bs] for b in range(len(self))), self._finish)

@@ -1,12 +1,12 @@
 """Batches for the detector, finished on the GPU: what `SSD300.loss`, `MultiBoxLoss.from_heads` and `SSD300.detect` take.
 
-Built like `GpuAugmentLoader` (gpu_loader.py).  A DataLoader (workers, pinned memory) yields the host side of a batch --
+A `StagedLoader` (staging.py), as `GpuAugmentLoader` is.  A DataLoader (workers, pinned memory) yields the host side of a batch --
 whole frames packed in one buffer plus a descriptor table, boxes and labels (`collate_frames`).  For each batch the main
 process draws the parameters, runs the box arithmetic, builds the kernel records, uploads records | boxes | labels | counts
 in ONE pinned copy and launches `t3d_detect_augment_u8` once (csrc/detect_augment.hip).  With `prefetch` >= 1 that work runs
 on a copy stream `prefetch` batches ahead of the consumer and each batch is handed over with an event the consumer's stream
-waits on; `prefetch = 0` does it synchronously on the consumer's stream.  Only the pinned staging rotates, each buffer
-guarded by the event of its last upload.
+waits on; `prefetch = 0` does it synchronously on the consumer's stream.  The pinned staging, the packed upload, the copy
+stream and that loop are staging.py's.
 
 Yields device tensors `(imgs uint8 [B, oh, ow, 3], gt_boxes float32 [B, G, 4] in input pixels, gt_labels int32 [B, G],
 gt_counts int32 [B])`, G the batch's largest count (at least 1), rows past a count zero.  A pipeline that is `Resize` alone
@@ -27,25 +27,23 @@ copies the frames of files the index keeps on the host into their slots and call
 front of the augment launch.  The frame table comes from the index; prefetch, staging rotation, keys and the yielded tuple are
 the same, and so are the batches, bit for bit.  `last_status` is the device status vector of the last decode call.
 """
-import collections
-
 import numpy as np
 import torch
 
 from .. import _native as N
-from .detection import collate_frames
+from .detection import collate_frames, resize_boxes
 from .jpeg import collate_jpeg, launch_decode, plan_batch
-from .objectron import AUG_SAMPLE_DTYPE
+from .objectron import resize_records
+from .staging import StagedLoader, upload
 
 __all__ = ['GpuDetectionLoader']
 
 
-class GpuDetectionLoader:
-    NBUF = 3            # pinned staging buffers in rotation
-
+class GpuDetectionLoader(StagedLoader):
     def __init__(self, dataset, pipeline, batch_size, sampler=None, shuffle=False, num_workers=0, drop_last=False, seed=0,
                  rank=0, prefetch=1):
-        self.pipeline, self.seed, self.rank, self.prefetch = pipeline, int(seed), int(rank), int(prefetch)
+        super().__init__(prefetch, min_staging=1 << 16)
+        self.pipeline, self.seed, self.rank = pipeline, int(seed), int(rank)
         # ObjectronFrames(decode='device') -- directly or under a Subset: byte items, decoded in `finish` (dataloaders/jpeg.py)
         self._frames = getattr(dataset, 'dataset', dataset)
         self.decode = getattr(self._frames, 'decode', 'host')
@@ -56,9 +54,6 @@ class GpuDetectionLoader:
                                                   collate_fn=collate_jpeg if self.decode == 'device' else collate_frames,
                                                   pin_memory=torch.cuda.is_available(), drop_last=drop_last)
         self.dataset, self.batch_size = dataset, batch_size
-        self._slots = [[None, None] for _ in range(self.NBUF)]     # (pinned host buffer, event after its upload)
-        self._turn = 0
-        self._copy_stream = None
 
     @property
     def sampler(self):
@@ -66,15 +61,6 @@ class GpuDetectionLoader:
 
     def __len__(self):
         return len(self.loader)
-
-    def _staging(self, nbytes):
-        slot = self._slots[self._turn]
-        self._turn = (self._turn + 1) % self.NBUF
-        if slot[1] is not None:
-            slot[1].synchronize()                  # the upload that last read this buffer has completed
-        if slot[0] is None or slot[0].numel() < nbytes:
-            slot[0] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
-        return slot
 
     def host_batch(self, host_batch, key_tail):
         """The host half of `finish`: draws, boxes and records of one collated batch.
@@ -84,18 +70,15 @@ class GpuDetectionLoader:
         B = len(dnp)
         cuts = np.cumsum(cnt)[:-1]
         bl, ll = np.split(boxes.numpy(), cuts), np.split(labels.numpy(), cuts)
-        oh, ow = self.pipeline.size
         if self.pipeline.random:
             epoch = int(getattr(self.loader.sampler, 'epoch', 0))
             prm = self.pipeline.draw(B, (self.seed, epoch, self.rank) + tuple(key_tail))
             bl, ll = self.pipeline.boxes(bl, ll, dnp, prm)
             rec = self.pipeline.records(dnp, prm)
         else:
-            rec = np.zeros(B, AUG_SAMPLE_DTYPE)          # flags 0: the resize alone
-            rec['offset'], rec['h'], rec['w'] = dnp[:, 0], dnp[:, 1], dnp[:, 2]
-            for i in range(B):                           # mmdet's Resize: scale, then clip to the image
-                sc = np.array([ow / dnp[i, 2], oh / dnp[i, 1]] * 2, np.float32)
-                bl[i] = np.minimum(np.maximum(bl[i] * sc, np.float32(0)), np.array([ow, oh, ow, oh], np.float32))
+            rec = resize_records(dnp)
+            row = np.repeat(np.arange(B), cnt)
+            bl = np.split(resize_boxes(boxes.numpy(), row, dnp[:, 1], dnp[:, 2], self.pipeline.size), cuts)
         G = max([len(l) for l in ll] + [1])
         gb, gl = np.zeros((B, G, 4), np.float32), np.zeros((B, G), np.int32)
         gc = np.asarray([len(l) for l in ll], np.int32)
@@ -106,6 +89,10 @@ class GpuDetectionLoader:
     def finish(self, host_batch, key_tail, prefetch=None):
         """One host batch -> the device tuple, enqueued on the copy stream (prefetch >= 1: the ready event is appended) or on
         the current stream (prefetch 0)."""
+        return self._public(*self._finish(host_batch, key_tail, prefetch))
+
+    def _finish(self, host_batch, key_tail, prefetch=None):
+        """-> (the device tuple, ready event or None)."""
         prefetch = self.prefetch if prefetch is None else prefetch
         packed, plan, fallback = host_batch[0], None, ()
         if self.decode == 'device':
@@ -128,23 +115,10 @@ class GpuDetectionLoader:
                  shapes.reshape(-1).view(np.uint8)]
         if plan is not None:                   # the batch's index rows ride in the same pinned copy
             parts += [plan['infos'].view(np.uint8), plan['segs'].view(np.uint8), plan['items'].view(np.uint8)]
-        offs = np.concatenate([[0], np.cumsum([(p.size + 7) // 8 * 8 for p in parts])])      # each part 8-byte aligned
-        total = int(offs[-1])
-        slot = self._staging(total)
-        host = slot[0]
-        for p, o in zip(parts, offs):
-            host[o:o + p.size].numpy()[...] = p
         dev = torch.device('cuda', torch.cuda.current_device())
-        stream = torch.cuda.current_stream(dev)
-        if prefetch > 0:
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(device=dev)
-            stream = self._copy_stream
+        stream = self._stream(dev, prefetch)
+        up = upload(self._ring, parts, stream, dev)
         with torch.cuda.stream(stream):
-            meta = torch.empty(max(total, 8), dtype=torch.uint8, device=dev)
-            meta[:total].copy_(host[:total], non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record(stream)
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
             src = packed.to(dev, non_blocking=True)
             if self.decode == 'device':
@@ -152,42 +126,13 @@ class GpuDetectionLoader:
                 for at, to, n in fallback:     # frames the host had to decode go to their slots as they are
                     src[to:to + n].copy_(raw[at:at + n], non_blocking=True)
                 if plan is not None:
-                    tabs = [meta[offs[k]:offs[k] + parts[k].size] for k in (5, 6, 7)]
-                    self.last_status = launch_decode(raw, *tabs, plan, src)
+                    self.last_status = launch_decode(raw, *[up.part(k, torch.uint8, -1) for k in (5, 6, 7)], plan, src)
             N.call('t3d_detect_augment_u8' if self.pipeline.random else 't3d_augment_crops_u8', N.ptr(src), src.numel(),
-                   N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
-
-            def part(k, dtype, *shape):
-                return meta[offs[k]:offs[k] + parts[k].size].view(dtype).view(*shape)
-            out = [imgs, part(1, torch.float32, B, G, 4), part(2, torch.int32, B, G), part(3, torch.int32, B)]
-            if not self.pipeline.random:
-                out.append(part(4, torch.int32, B, 2))
-        if prefetch > 0:
-            ready = torch.cuda.Event()
-            ready.record(stream)
-            out.append(ready)
-        return tuple(out)
+                   N.ptr(up.part(0, torch.uint8, -1)), N.ptr(imgs), B, oh, ow, N.stream())
+        out = (imgs, up.part(1, torch.float32, B, G, 4), up.part(2, torch.int32, B, G), up.part(3, torch.int32, B))
+        if not self.pipeline.random:
+            out += (up.part(4, torch.int32, B, 2),)
+        return out, self._ready(stream, prefetch)
 
     def __iter__(self):
-        it = iter(self.loader)
-        pending, done, b = collections.deque(), False, 0
-        while True:
-            while not done and len(pending) <= self.prefetch:
-                try:
-                    hb = next(it)
-                except StopIteration:
-                    done = True
-                    break
-                pending.append(self.finish(hb, (b,)))
-                b += 1
-            if not pending:
-                return
-            out = pending.popleft()
-            if self.prefetch > 0:
-                *out, ready = out
-                consumer = torch.cuda.current_stream(out[0].device)
-                consumer.wait_event(ready)
-                for t in out[:2]:                # (boxes, labels, counts and shapes share one allocation)
-                    t.record_stream(consumer)
-                out = tuple(out)
-            yield out
+        yield from self._batches(iter(self.loader), self._finish)

@@ -9,8 +9,8 @@ batch i + 1 is uploaded and augmented while step i runs.  `prefetch = 0` does it
 
 Yields device tensors `(imgs uint8 [B, oh, ow, 3], keypoints float32 [B, 9, 2], classes int64 [B])`: `Trainer.train`,
 `Evaluator.val` and the step plan take them as they are.  The yielded tensors belong to the consumer (fresh allocations,
-recorded on the consumer's stream); only the pinned staging of the records rotates, each buffer guarded by the event of its
-last upload (the rule FrameCropper follows).
+recorded on the consumer's stream); the pinned staging of the records, the one packed upload, the copy stream and the prefetch
+loop are `StagedLoader`'s (staging.py).
 
 `cache='device'` (`cfg.data.cache`): the pipeline resizes first, so resize(crop(frame)) is the same [oh, ow, 3] image in
 every epoch.  One pass over the dataset (`fill_cache`, run at the first `__iter__`) decodes every object once and stores that
@@ -20,13 +20,12 @@ same batches, sharding and `set_epoch`), draws the same parameters with the same
 `t3d_augment_resized_u8` over the arena: no worker, no decode, no upload of pixels, and batches equal to the uncached
 loader's bit for bit.  The arena must fit `cache_max_gb`; there is no partial cache.
 """
-import collections
-
 import numpy as np
 import torch
 
 from .. import _native as N
-from .objectron import AUG_SAMPLE_DTYPE, chain_scratch_bytes, chain_stages, collate_crops
+from .objectron import chain_scratch_bytes, chain_stages, collate_crops, resize_records
+from .staging import StagedLoader, upload
 
 __all__ = ['GpuAugmentLoader']
 
@@ -52,12 +51,11 @@ class _FinishedDataset:
         return imgs[0], kp[0], int(cats[0])
 
 
-class GpuAugmentLoader:
-    NBUF = 3            # pinned record buffers in rotation
-
+class GpuAugmentLoader(StagedLoader):
     def __init__(self, dataset, pipeline, batch_size, sampler=None, shuffle=False, num_workers=0, drop_last=False, seed=0,
                  rank=0, prefetch=1, cache=None, cache_max_gb=32):
-        self.pipeline, self.seed, self.rank, self.prefetch = pipeline, int(seed), int(rank), int(prefetch)
+        super().__init__(prefetch, min_staging=1 << 16)
+        self.pipeline, self.seed, self.rank = pipeline, int(seed), int(rank)
         self.cache = cache or None
         if self.cache is not None:
             if self.cache != 'device':
@@ -76,9 +74,6 @@ class GpuAugmentLoader:
                                                   pin_memory=torch.cuda.is_available(), drop_last=drop_last)
         self.dataset = _FinishedDataset(dataset, self)
         self.batch_size = batch_size
-        self._slots = [[None, None] for _ in range(self.NBUF)]     # (pinned host buffer, event after its upload)
-        self._turn = 0
-        self._copy_stream = None
 
     @property
     def sampler(self):
@@ -87,24 +82,21 @@ class GpuAugmentLoader:
     def __len__(self):
         return len(self.loader)
 
-    def _staging(self, nbytes):
-        slot = self._slots[self._turn]
-        self._turn = (self._turn + 1) % self.NBUF
-        if slot[1] is not None:
-            slot[1].synchronize()                  # the upload that last read this buffer has completed
-        if slot[0] is None or slot[0].numel() < nbytes:
-            slot[0] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
-        return slot
-
     def finish(self, host_batch, key_tail, prefetch=None):
         """One host batch -> device (imgs, keypoints, classes), enqueued on the copy stream (prefetch >= 1, with an event the
         caller hands to its consumer) or on the current stream (prefetch 0).  -> (imgs, kp, cats[, ready event])."""
+        return self._public(*self._finish_batch(host_batch, key_tail, prefetch))
+
+    def finish_cached(self, indices, key_tail, prefetch=None):
+        """`finish` for a batch of dataset indices whose resized crops are in the arena."""
+        return self._public(*self._finish_indices(indices, key_tail, prefetch))
+
+    def _finish_batch(self, host_batch, key_tail, prefetch=None):
         packed, desc, kp64, cats = host_batch
         dnp = desc.numpy()
         return self._finish(packed, dnp, dnp, kp64.numpy(), cats.numpy(), key_tail, prefetch)
 
-    def finish_cached(self, indices, key_tail, prefetch=None):
-        """`finish` for a batch of dataset indices whose resized crops are in the arena."""
+    def _finish_indices(self, indices, key_tail, prefetch=None):
         idx = np.asarray(indices, np.int64)
         oh, ow = self.pipeline.size
         where = np.stack([idx * (oh * ow * 3), np.full_like(idx, oh), np.full_like(idx, ow)], 1)     # (slot offset, oh, ow)
@@ -112,7 +104,7 @@ class GpuAugmentLoader:
 
     def _finish(self, packed, where, dnp, kp64, cats, key_tail, prefetch):
         """where [B, 3]: (offset, h, w) of the kernel's source images (the packed crops, or arena slots when `packed` is
-        None); dnp [B, 3]: the real crop sizes, which scale the keypoints."""
+        None); dnp [B, 3]: the real crop sizes, which scale the keypoints.  -> ((imgs, kp, cats), ready event or None)."""
         prefetch = self.prefetch if prefetch is None else prefetch
         B = int(where.shape[0])
         oh, ow = self.pipeline.size
@@ -123,47 +115,27 @@ class GpuAugmentLoader:
         if self.pipeline.chained:
             rec, ext = rec
         kp = self.pipeline.keypoints(kp64, dnp, prm)
-        # one pinned upload for records | keypoints | classes [| chain records] (each part 8-byte aligned)
-        nrec, nkp = B * rec.dtype.itemsize, B * 18 * 4
-        nkp8 = (nkp + 7) // 8 * 8
-        next_ = nrec + nkp8 + B * 8
-        total = next_ + (B * ext.dtype.itemsize if ext is not None else 0)
-        slot = self._staging(total)
-        host = slot[0]
-        host[:nrec].numpy()[...] = rec.view(np.uint8)
-        host[nrec:nrec + nkp].numpy()[...] = kp.reshape(-1).view(np.uint8)
-        host[nrec + nkp8:next_].numpy()[...] = cats.astype(np.int64).view(np.uint8)
+        # one pinned upload for records | keypoints | classes [| chain records]
+        parts = [rec.view(np.uint8), kp.reshape(-1).view(np.uint8), cats.astype(np.int64).view(np.uint8)]
         if ext is not None:
-            host[next_:total].numpy()[...] = ext.view(np.uint8)
+            parts.append(ext.view(np.uint8))
         dev = torch.device('cuda', torch.cuda.current_device())
-        stream = torch.cuda.current_stream(dev)
-        if prefetch > 0:
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(device=dev)
-            stream = self._copy_stream
+        stream = self._stream(dev, prefetch)
+        up = upload(self._ring, parts, stream, dev)
         with torch.cuda.stream(stream):
-            meta = torch.empty(total, dtype=torch.uint8, device=dev)
-            meta.copy_(host[:total], non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record(stream)
+            recd = up.part(0, torch.uint8, -1)
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
             src = self._arena if packed is None else packed.to(dev, non_blocking=True)
             if ext is None:
                 N.call('t3d_augment_resized_u8' if packed is None else 't3d_augment_crops_u8', N.ptr(src), src.numel(),
-                       N.ptr(meta), N.ptr(imgs), B, oh, ow, N.stream())
+                       N.ptr(recd), N.ptr(imgs), B, oh, ow, N.stream())
             elif B:
                 stages = chain_stages(rec, ext)
                 scratch = torch.empty(max(chain_scratch_bytes(B, oh, ow, stages), 8), dtype=torch.uint8, device=dev)
                 N.call('t3d_augment_chain_resized_u8' if packed is None else 't3d_augment_chain_crops_u8', N.ptr(src),
-                       src.numel(), N.ptr(meta), N.ptr(meta[next_:total]), N.ptr(scratch), scratch.numel(), N.ptr(imgs), B,
-                       oh, ow, stages, N.stream())
-            kp_d = meta[nrec:nrec + nkp].view(torch.float32).view(B, 9, 2)
-            cats_d = meta[nrec + nkp8:next_].view(torch.int64)
-        if prefetch > 0:
-            ready = torch.cuda.Event()
-            ready.record(stream)
-            return imgs, kp_d, cats_d, ready
-        return imgs, kp_d, cats_d
+                       src.numel(), N.ptr(recd), N.ptr(up.part(3, torch.uint8, -1)), N.ptr(scratch), scratch.numel(),
+                       N.ptr(imgs), B, oh, ow, stages, N.stream())
+        return (imgs, up.part(1, torch.float32, B, 9, 2), up.part(2, torch.int64, B)), self._ready(stream, prefetch)
 
     def fill_cache(self):
         """The one decode pass: every dataset index, in order, through a DataLoader with the configured workers; its resized
@@ -182,10 +154,8 @@ class GpuAugmentLoader:
         i0 = 0
         for packed, desc, kp64, cats in it:
             B = int(desc.shape[0])
-            rec = np.zeros(B, AUG_SAMPLE_DTYPE)          # flags 0: the resize alone
             dnp = desc.numpy()
-            rec['offset'], rec['h'], rec['w'] = dnp[:, 0], dnp[:, 1], dnp[:, 2]
-            recd = torch.from_numpy(rec.view(np.uint8)).to(dev)
+            recd = torch.from_numpy(resize_records(dnp).view(np.uint8)).to(dev)
             src = packed.to(dev, non_blocking=True)
             out = arena[i0 * slot:(i0 + B) * slot]
             if out.data_ptr() & 3:                             # the kernel stores dwords: an odd slot goes through a staging tensor
@@ -206,27 +176,6 @@ class GpuAugmentLoader:
     def __iter__(self):
         if self.cache is not None:
             self.fill_cache()
-            it, finish = iter(self.loader.batch_sampler), self.finish_cached
+            yield from self._batches(iter(self.loader.batch_sampler), self._finish_indices)
         else:
-            it, finish = iter(self.loader), self.finish
-        pending, done, b = collections.deque(), False, 0
-        while True:
-            while not done and len(pending) <= self.prefetch:
-                try:
-                    hb = next(it)
-                except StopIteration:
-                    done = True
-                    break
-                pending.append(finish(hb, (b,)))
-                b += 1
-            if not pending:
-                return
-            out = pending.popleft()
-            if self.prefetch > 0:
-                imgs, kp, cats, ready = out
-                consumer = torch.cuda.current_stream(imgs.device)
-                consumer.wait_event(ready)
-                for t in (imgs, kp):             # (kp and cats share one allocation)
-                    t.record_stream(consumer)
-                out = (imgs, kp, cats)
-            yield out
+            yield from self._batches(iter(self.loader), self._finish_batch)

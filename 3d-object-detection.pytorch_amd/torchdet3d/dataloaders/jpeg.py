@@ -28,10 +28,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .staging import pack
+
 __all__ = ['JpegIndex', 'decode_jpeg_batch', 'index_jpeg', 'collate_jpeg', 'INFO_DTYPE', 'SEG_DTYPE', 'ITEM_DTYPE',
            'DEFAULT_SEG_MCUS', 'REASONS', 'roi_mcus', 'plan_roi', 'plan_roi_batch', 'launch_decode_roi', 'decode_jpeg_rois',
            'ROI_SEG_MCUS', 'ROI_READ_AHEAD', 'read_jpeg_header', 'index_jpeg_device', 'decode_jpeg_frames', 'DEFAULT_SUB_BYTES',
-           'SUB_BYTES_RANGE']
+           'SUB_BYTES_RANGE', 'launch_decode', 'starts', 'mcu_blocks', 'frame_blocks', 'item_table']
 
 # include/t3d.h: t3d_jpeg_info (864 bytes), t3d_jpeg_seg (16), t3d_jpeg_item (48)
 INFO_DTYPE = np.dtype([('h', '<i4'), ('w', '<i4'), ('ncomp', '<i4'), ('sampling', '<i4'), ('mcus_x', '<i4'), ('mcus_y', '<i4'),
@@ -86,6 +88,37 @@ def read_jpeg_header(data, seg_mcus=DEFAULT_SEG_MCUS):
     return rc, info[0]
 
 
+def _reason(rc, info):
+    """The return code of t3d_jpeg_index / t3d_jpeg_header and the record it filled -> the key of REASONS."""
+    from .. import _native as N
+    return 0 if rc == 0 else (int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1)
+
+
+def starts(counts):
+    """counts [n] -> int64 [n]: where each begins when they lie one behind the other."""
+    counts = np.asarray(counts, np.int64)
+    return np.cumsum(counts) - counts
+
+
+def mcu_blocks(sampling):
+    """8x8 blocks of one MCU, by T3D_JPEG_GRAY / _444 / _420 (a record the device does not decode may hold any value)."""
+    return np.asarray(_BLOCKS_PER_MCU, np.int64)[np.clip(sampling, 0, 2)]
+
+
+def frame_blocks(infos):
+    """INFO_DTYPE records -> int64: the 8x8 blocks of each whole frame."""
+    return infos['mcus_x'].astype(np.int64) * infos['mcus_y'] * mcu_blocks(infos['sampling'])
+
+
+def item_table(file_offset, file_bytes, out_offset, seg_offset, blocks):
+    """The t3d_jpeg_item table of one call: where each file's bytes, frame and segment rows lie, and `block_offset`, the
+    prefix sums of `blocks` (the decode's 8x8 blocks, the device indexer's subsequence records)."""
+    items = np.zeros(len(blocks), ITEM_DTYPE)
+    items['file_offset'], items['file_bytes'], items['out_offset'] = file_offset, file_bytes, out_offset
+    items['seg_offset'], items['block_offset'] = seg_offset, starts(blocks)
+    return items
+
+
 class JpegIndex:
     """The index of a list of files, as flat numpy arrays: `infos` [n] INFO_DTYPE, `segs` [total] SEG_DTYPE, `seg_start` int64
     [n + 1] (file i owns segs[seg_start[i]:seg_start[i + 1]]), `size` and `mtime_ns` int64 [n] of the file when it was indexed,
@@ -115,10 +148,13 @@ class JpegIndex:
             path = os.path.join(str(root), name)
             st = os.stat(path)
             rc, info, segs = index_jpeg(np.fromfile(path, np.uint8), seg_mcus)
-            reason = 0 if rc == 0 else (int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1)
-            return info, segs, st.st_size, st.st_mtime_ns, reason
+            return info, segs, st.st_size, st.st_mtime_ns, _reason(rc, info)
         with ThreadPoolExecutor(max_workers=threads) as ex:
-            rows = list(ex.map(one, files))
+            return cls._from_rows(files, list(ex.map(one, files)), seg_mcus)
+
+    @classmethod
+    def _from_rows(cls, files, rows, seg_mcus):
+        """rows: (info, segs, size, mtime_ns, reason) of each file -> the index of the flat arrays."""
         infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
         seg_start = np.concatenate([[0], np.cumsum([len(r[1]) for r in rows])]).astype(np.int64)
         segs = np.concatenate([r[1] for r in rows] + [np.zeros(0, SEG_DTYPE)])
@@ -128,8 +164,6 @@ class JpegIndex:
     @classmethod
     def _build_device(cls, files, root, seg_mcus, threads):
         import torch
-
-        from .. import _native as N
         if not torch.cuda.is_available():
             raise RuntimeError("JpegIndex.build(where='device') needs a GPU and none is present: build with where='host'")
 
@@ -157,15 +191,11 @@ class JpegIndex:
                         info, segs, reason = done[k]
                     elif rc == 0:                       # the device refuses its scan: the host indexer says why, in its own words
                         rc, info, segs = index_jpeg(data, seg_mcus)
-                        reason = 0 if rc == 0 else (int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1)
+                        reason = _reason(rc, info)
                     else:
-                        segs, reason = np.zeros(0, SEG_DTYPE), int(info['reason']) if rc == N.ERR_UNSUPPORTED else -1
+                        segs, reason = np.zeros(0, SEG_DTYPE), _reason(rc, info)
                     rows.append((info, segs, size, mtime, reason))
-        infos = np.array([r[0] for r in rows], INFO_DTYPE).reshape(-1)
-        seg_start = np.concatenate([[0], np.cumsum([len(r[1]) for r in rows])]).astype(np.int64)
-        segs = np.concatenate([r[1] for r in rows] + [np.zeros(0, SEG_DTYPE)])
-        return cls(files, infos, segs, seg_start, np.array([r[2] for r in rows], np.int64), np.array([r[3] for r in rows], np.int64),
-                   np.array([r[4] for r in rows], np.int64), seg_mcus)
+        return cls._from_rows(files, rows, seg_mcus)
 
     def rows(self, i):
         """-> (info record, segment table) of file i: what `decode_jpeg_batch` takes."""
@@ -256,24 +286,21 @@ def plan_batch(rows, file_offsets, file_sizes, out_offsets):
     max_segs, max_blocks)."""
     infos = _checked_infos(rows)
     segs = np.concatenate([np.asarray(r[1]) for r in rows] + [np.zeros(0, SEG_DTYPE)])
-    blocks = infos['mcus_x'].astype(np.int64) * infos['mcus_y'] * np.asarray(_BLOCKS_PER_MCU, np.int64)[infos['sampling']]
-    items = np.zeros(len(rows), ITEM_DTYPE)
-    items['file_offset'], items['file_bytes'], items['out_offset'] = file_offsets, file_sizes, out_offsets
-    items['block_offset'] = np.cumsum(blocks) - blocks
-    items['seg_offset'] = np.cumsum(infos['nseg'].astype(np.int64)) - infos['nseg']
+    blocks = frame_blocks(infos)
+    items = item_table(file_offsets, file_sizes, out_offsets, starts(infos['nseg']), blocks)
     return dict(infos=infos, segs=segs, items=items, total_segs=len(segs), total_blocks=int(blocks.sum()),
                 max_segs=int(infos['nseg'].max()), max_blocks=int(blocks.max()))
 
 
-def _launch(entry, data, infos, segs, tables, plan, out, bounds):
-    """Workspace and status vector of one decode call, then the call on the current stream.  tables: the device tensors between
-    `segs` and `out` in the entry's argument list; bounds: the plan's keys of the entry's grid bounds.  -> status, int32 [B]."""
+def _launch(entry, B, data, infos, segs, tables, plan, out, bounds):
+    """Workspace and status vector of one decode call over B items, then the call on the current stream.  tables: the device
+    tensors between `segs` and `out` in the entry's argument list; bounds: the plan's keys of the entry's grid bounds.
+    -> status, int32 [B]."""
     import ctypes
 
     import torch
 
     from .. import _native as N
-    B = len(plan['infos'])
     nbytes = ctypes.c_longlong(0)
     if N.lib().t3d_jpeg_decode_work_bytes(plan['total_blocks'], ctypes.byref(nbytes)) != 0:
         raise RuntimeError('t3d_jpeg_decode_work_bytes failed')
@@ -286,8 +313,11 @@ def _launch(entry, data, infos, segs, tables, plan, out, bounds):
 
 def launch_decode(data, infos, segs, items, plan, out):
     """Enqueue t3d_jpeg_decode_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items: device uint8
-    tensors holding plan['infos'], ['segs'], ['items'].  -> status, device int32 [B] (0: decoded to the last MCU)."""
-    return _launch('t3d_jpeg_decode_u8', data, infos, segs, (items,), plan, out, ('max_segs', 'max_blocks'))
+    tensors holding the B items' t3d_jpeg_info records, the segment rows their `seg_offset` points into and their t3d_jpeg_item
+    table (`plan_batch`: plan['infos'], ['segs'], ['items']); plan: total_segs (rows in `segs`), total_blocks, max_segs,
+    max_blocks.  -> status, device int32 [B] (0: decoded to the last MCU)."""
+    return _launch('t3d_jpeg_decode_u8', items.numel() // ITEM_DTYPE.itemsize, data, infos, segs, (items,), plan, out,
+                   ('max_segs', 'max_blocks'))
 
 
 def _packed(sizes, dev):
@@ -302,10 +332,11 @@ def _packed(sizes, dev):
 
 
 def _upload_parts(parts, dev):
-    """numpy uint8 arrays -> their device views inside ONE uploaded buffer (each part 16-byte aligned)."""
+    """numpy uint8 arrays -> their device views inside ONE uploaded buffer (`pack`), through pageable memory: the upload has
+    run when this returns, which the one-call forms below rely on."""
     import torch
-    offs = np.concatenate([[0], np.cumsum([-(-p.size // 16) * 16 for p in parts])])
-    host = np.zeros(max(int(offs[-1]), 16), np.uint8)
+    offs, total = pack(parts)
+    host = np.zeros(max(total, 16), np.uint8)
     for p, o in zip(parts, offs):
         host[o:o + p.size] = p
     d = torch.from_numpy(host).to(dev)
@@ -351,8 +382,7 @@ def _index_device(files, seg_mcus, sub_bytes, device, decode=False):
     for i, a in enumerate(arrs):
         rc, heads[i] = read_jpeg_header(a, seg_mcus)
         if rc != 0:
-            raise ValueError(f'file {i} of the batch is not decoded on the device: '
-                             f'{REASONS[int(heads[i]["reason"]) if rc == N.ERR_UNSUPPORTED else -1]}')
+            raise ValueError(f'file {i} of the batch is not decoded on the device: {REASONS[_reason(rc, heads[i])]}')
     B = len(arrs)
     sizes = np.array([a.size for a in arrs], np.int64)
     nseg = heads['nseg'].astype(np.int64)
@@ -363,15 +393,12 @@ def _index_device(files, seg_mcus, sub_bytes, device, decode=False):
         return dict(data=empty, infos=empty, segs=empty, items=empty, status=status[:0], seg_start=seg_start, heads=heads, plan=None,
                     work=empty)
     nsub = -(-heads['scan_bytes'].astype(np.int64) // sub_bytes)
-    blocks = heads['mcus_x'].astype(np.int64) * heads['mcus_y'] * np.asarray(_BLOCKS_PER_MCU, np.int64)[heads['sampling']]
-    items = np.zeros(B, ITEM_DTYPE)
-    items['file_offset'], items['file_bytes'] = np.cumsum(sizes) - sizes, sizes
-    items['seg_offset'], items['block_offset'] = seg_start[:-1], np.cumsum(nsub) - nsub      # block_offset: subsequence records
+    blocks = frame_blocks(heads)
+    items = item_table(starts(sizes), sizes, 0, seg_start[:-1], nsub)      # block_offset: subsequence records
     parts = [np.concatenate(arrs), heads.view(np.uint8), items.view(np.uint8)]
     if decode:
-        ditems = items.copy()
-        nb = heads['h'].astype(np.int64) * heads['w'] * 3
-        ditems['out_offset'], ditems['block_offset'] = np.cumsum(nb) - nb, np.cumsum(blocks) - blocks
+        frame_bytes = heads['h'].astype(np.int64) * heads['w'] * 3
+        ditems = item_table(items['file_offset'], sizes, starts(frame_bytes), seg_start[:-1], blocks)
         parts.append(ditems.view(np.uint8))
     parts = _upload_parts(parts, dev)
     total_segs = int(seg_start[-1])
@@ -382,7 +409,7 @@ def _index_device(files, seg_mcus, sub_bytes, device, decode=False):
     work = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
     N.call('t3d_jpeg_index_device', N.ptr(parts[0]), parts[0].numel(), N.ptr(parts[1]), N.ptr(segs), total_segs, N.ptr(parts[2]), sub_bytes,
            N.ptr(work), work.numel(), N.ptr(status), B, int(nsub.max()), N.stream())
-    plan = dict(infos=heads, total_segs=total_segs, total_blocks=int(blocks.sum()), max_segs=int(nseg.max()), max_blocks=int(blocks.max()))
+    plan = dict(total_segs=total_segs, total_blocks=int(blocks.sum()), max_segs=int(nseg.max()), max_blocks=int(blocks.max()))
     return dict(data=parts[0], infos=parts[1], segs=segs, items=parts[-1], status=status[:B], seg_start=seg_start, heads=heads, plan=plan,
                 work=work)
 
@@ -466,7 +493,7 @@ def plan_roi(info, segs, x0, y0, x1, y1):
     end = min(int(segs[s_hi + 1]['byte']) + ROI_READ_AHEAD, scan_bytes) if s_hi + 1 < int(info['nseg']) else scan_bytes
     rw, rh = mx1 - mx0, my1 - my0
     return dict(rect=(x0, y0, x1, y1), mcus=(mx0, my0, mx1, my1), row_segs=row_segs, seg_first=s_lo, seg_count=s_hi - s_lo + 1,
-                span=(first, end - first), blocks=rw * rh * _BLOCKS_PER_MCU[int(info['sampling'])],
+                span=(first, end - first), blocks=rw * rh * int(mcu_blocks(info['sampling'])),
                 lanes=rh * ((rw - 1) // S + 2), runs=(y1 - y0) * ((x1 - x0 + 3) // 4))
 
 
@@ -481,10 +508,8 @@ def plan_roi_batch(rows, plans, data_offsets, out_offsets, spans=None):
     spans = [p['span'] for p in plans] if spans is None else spans
     nseg = np.array([p['seg_count'] for p in plans], np.int64)
     blocks = np.array([p['blocks'] for p in plans], np.int64)
-    items = np.zeros(len(rows), ITEM_DTYPE)
-    items['file_offset'], items['out_offset'] = data_offsets, out_offsets
-    items['reserved'], items['file_bytes'] = [s[0] for s in spans], [s[1] for s in spans]
-    items['block_offset'], items['seg_offset'] = np.cumsum(blocks) - blocks, np.cumsum(nseg) - nseg
+    items = item_table(data_offsets, [s[1] for s in spans], out_offsets, starts(nseg), blocks)
+    items['reserved'] = [s[0] for s in spans]
     rects = np.zeros((len(rows), 12), np.int32)
     for k, p in enumerate(plans):
         rects[k, :10] = p['rect'] + p['mcus'] + (p['seg_first'], p['seg_count'])
@@ -495,7 +520,8 @@ def plan_roi_batch(rows, plans, data_offsets, out_offsets, spans=None):
 def launch_decode_roi(data, infos, segs, items, rects, plan, out):
     """Enqueue t3d_jpeg_decode_roi_u8 on the current stream.  data, out: device uint8 tensors; infos, segs, items, rects: device
     uint8 tensors holding plan['infos'], ['segs'], ['items'], ['rects'] (`plan_roi_batch`).  -> status, device int32 [B]."""
-    return _launch('t3d_jpeg_decode_roi_u8', data, infos, segs, (items, rects), plan, out, ('max_lanes', 'max_blocks', 'max_runs'))
+    return _launch('t3d_jpeg_decode_roi_u8', items.numel() // ITEM_DTYPE.itemsize, data, infos, segs, (items, rects), plan, out,
+                   ('max_lanes', 'max_blocks', 'max_runs'))
 
 
 def decode_jpeg_rois(files, rows, rects, device=None, partial=True):

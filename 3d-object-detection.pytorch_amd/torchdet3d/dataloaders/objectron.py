@@ -33,7 +33,7 @@ from ..utils import OBJECTRON_CLASSES
 from .gpu_crops import crop_cords_from_keypoints
 
 __all__ = ['Objectron', 'AugmentPipeline', 'build_augmentations', 'collate_crops', 'AUG_SAMPLE_DTYPE', 'AUG_CHAIN_DTYPE',
-           'chain_stages', 'chain_scratch_bytes']
+           'chain_stages', 'chain_scratch_bytes', 'resize_records']
 
 # include/t3d.h: t3d_aug_sample (80 bytes) and its flags
 AUG_SAMPLE_DTYPE = np.dtype([('offset', '<i8'), ('h', '<i4'), ('w', '<i4'), ('flags', '<i4'), ('alpha', '<f4'),
@@ -52,6 +52,13 @@ STAGE_MEAN, STAGE_WARP, STAGE_WARP2 = 1, 2, 4
 # key, and no item index -- the last component of an item key -- reaches the tag, so it equals no key the loader draws with.
 _CHAIN_TAG = 0x7C4A1F3B9D5E
 _JITTER_ORDERS = np.array(list(itertools.permutations(range(4))), np.int64)      # 24 orders of (b, c, s, h)
+
+
+def resize_records(desc):
+    """desc [B, 3] = (offset, h, w) of the source images -> their t3d_aug_sample records with no flag set: the resize alone."""
+    rec = np.zeros(len(desc), AUG_SAMPLE_DTYPE)
+    rec['offset'], rec['h'], rec['w'] = desc[:, 0], desc[:, 1], desc[:, 2]
+    return rec
 
 
 def chain_stages(rec, ext):
@@ -352,8 +359,7 @@ class AugmentPipeline:
             return self._chain_records(desc, prm)
         oh, ow = self.size
         B = len(desc)
-        rec = np.zeros(B, AUG_SAMPLE_DTYPE)
-        rec['offset'], rec['h'], rec['w'] = desc[:, 0], desc[:, 1], desc[:, 2]
+        rec = resize_records(desc)
         flags = np.where(prm['flip'], AUG_FLIP, 0) | np.where(prm['lut'], AUG_LUT, 0) | np.where(prm['rot'], AUG_ROTATE, 0)
         rec['flags'] = flags | (AUG_SWAP_RB if self.swap else 0)
         rec['alpha'] = np.where(prm['lut'], prm['alpha'], 1.0).astype(np.float32)
@@ -366,8 +372,7 @@ class AugmentPipeline:
         """The base record carries the flip, the channel order and the FIRST warp that fires; the brightness / contrast LUT
         goes into the colour program, at its place in the config's order."""
         B = len(desc)
-        rec, ext = np.zeros(B, AUG_SAMPLE_DTYPE), np.zeros(B, AUG_CHAIN_DTYPE)
-        rec['offset'], rec['h'], rec['w'] = desc[:, 0], desc[:, 1], desc[:, 2]
+        rec, ext = resize_records(desc), np.zeros(B, AUG_CHAIN_DTYPE)
         rec['flags'] = np.where(prm['flip'], AUG_FLIP, 0) | (AUG_SWAP_RB if self.swap else 0)
         rec['alpha'] = 1.0
         jitter = (('jb', CHAIN_BRIGHTNESS), ('jc', CHAIN_CONTRAST), ('js', CHAIN_SATURATION), ('jh', CHAIN_HUE))

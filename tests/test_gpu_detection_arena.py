@@ -144,6 +144,29 @@ def test_the_arena_loader_yields_the_host_decoded_batches(tmp_path, with_host_de
         assert not train_a.last_status.cpu().numpy().any() and not val_a.last_status.cpu().numpy().any()
 
 
+def test_a_fill_of_more_chunks_than_staging_buffers_keeps_every_files_bytes(tmp_path, monkeypatch):
+    """`DetectionArena.fill` with one file a chunk: ten chunks through three pinned buffers, behind a stream that is running
+    late, so a buffer rewritten before its upload has run would put a later file's bytes in an earlier file's place."""
+    from torchdet3d.dataloaders import DetectionArena, ObjectronFrames
+    root = str(tmp_path / 'frames')
+    _write(root, _files(True))
+    fr = ObjectronFrames(root, 'val', decode='device')
+    fr.build_index(seg_mcus=2)
+    arena = DetectionArena(fr)
+    assert len(arena) == 10 >= 3 + 2 and list(np.flatnonzero(arena.kind)) == [5, 8]       # (three buffers rotate)
+    want = []
+    for i, name in enumerate(fr.files):
+        path = os.path.join(root, name)
+        want.append(fr._decode_host(path).reshape(-1) if arena.kind[i] else np.fromfile(path, np.uint8))
+    assert [len(w) for w in want] == list(arena.size)
+    monkeypatch.setattr(DetectionArena, 'STAGING', int(arena.size.min()))                 # below any two files: every chunk is one file
+    torch.cuda._sleep(100_000_000)
+    arena.fill()
+    torch.cuda.synchronize()
+    total = int(arena.size.sum())
+    assert arena.data.numel() >= total and np.array_equal(arena.data[:total].cpu().numpy(), np.concatenate(want))
+
+
 def test_two_train_steps_from_the_arena_give_the_host_loaders_losses(tmp_path):
     """The smallest detector configuration of tests/test_gpu_detector_train.py: SSD300 at 300 x 300, batches of 2, bf16 storage."""
     from torchdet3d.models.ssd import SSD300
