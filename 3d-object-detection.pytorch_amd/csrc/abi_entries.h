@@ -34,7 +34,7 @@
   S(t3d_ssd_head_bwd) S(t3d_ssd_cap_per_image) S(t3d_coco_match) \
   /* the rest: queries that return sizes / flags / routes, process-wide aids, the loaders' calls, the plan's own interface */ \
   Q(t3d_version) Q(t3d_pwconv_frag_bytes) Q(t3d_pwconv_wants_frag) Q(t3d_pwconv_route) Q(t3d_pwconv_force_route) \
-  Q(t3d_pwconv_bwd_yfree_scratch) Q(t3d_dwconv_route) Q(t3d_dwconv_force_route) \
+  Q(t3d_pwconv_bwd_yfree_scratch) Q(t3d_dwconv_route) Q(t3d_dwconv_plan) Q(t3d_dwconv_force_route) \
   Q(t3d_augment_crops_u8) Q(t3d_augment_resized_u8) Q(t3d_augment_chain_crops_u8) Q(t3d_augment_chain_resized_u8) \
   Q(t3d_detect_augment_u8) Q(t3d_detect_draw) Q(t3d_detect_draw_host) Q(t3d_jpeg_index) Q(t3d_jpeg_decode_work_bytes) Q(t3d_jpeg_decode_u8) Q(t3d_jpeg_decode_roi_u8) \
   Q(t3d_jpeg_header) Q(t3d_jpeg_index_work_bytes) Q(t3d_jpeg_index_device) \

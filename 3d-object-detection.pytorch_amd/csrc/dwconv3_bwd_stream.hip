@@ -19,7 +19,7 @@
 // t3d_dw_flush -- bit-reproducible; fp32 atomics into replicas when the caller provides no slots).
 #include <cstdlib>
 #include <type_traits>
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -43,48 +43,13 @@ struct Dw3BArgs {
   const T3dFold* fold;  // requested BatchNorm-backward finalize of (alpha, beta, gamma), derived in the prologue (common.h)
 };
 
-template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
-
 // ---------------------------------------------------------------------------------------------------------------
 // Two columns per thread + packed fp32 math (the stride-1 backward).  One column per thread (the header's skeleton, retired) needed
 // ~310 VALU instructions per output vector and was VALU-bound at ~1.2 TB/s; here four column loads of dz / y / x feed
 // two outputs (dy and the activations are formed twice per element instead of three times), every multiply-add is a
 // v_pk_fma_f32, and the 9 x CH stencil weights are read from LDS per use (saves 36 registers for the two
 // accumulator sets).  Padding: 0/1 masks per out-of-image column, wave-uniform row skips.
-// raw buffer load of one register vector: scalar descriptor + scalar byte offset + per-lane byte offset
-// relu6(s x + t) = 6 clamp01((s/6) x + t/6) in one packed instruction (v_pk_fma_f32 with the clamp modifier; bf16 storage
-// only, dwconv3_stream.hip has the note): the activated operand a' = a/6 feeds the weight gradient (the 6 is applied once,
-// when the accumulators are flushed) and IS the derivative mask of the own columns (0 < a' < 1)
-__device__ __forceinline__ f32x2 pk_fma_clamp01(f32x2 a, f32x2 b, f32x2 c) {
-  f32x2 d;
-  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
-template <typename RV>
-__device__ __forceinline__ RV bufload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  if constexpr (sizeof(RV) == 4) {
-    return __builtin_bit_cast(RV, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-  } else if constexpr (sizeof(RV) == 8) {
-    return __builtin_bit_cast(RV, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-  } else {
-    return __builtin_bit_cast(RV, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-  }
-}
-
-template <typename RV>
-__device__ __forceinline__ void bufstore(const RV& v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  if constexpr (sizeof(RV) == 4) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-  } else if constexpr (sizeof(RV) == 8) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, 0);
-  } else {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-  }
-}
-
+// (raw buffer loads / stores and the packed clamp form of ReLU6, pk_fma_clamp01: dwconv_walk.h)
 // ACT: the input's activation as a compile-time constant (a runtime switch in the row loop costs a scalar branch chain
 // and a register-merge of all variants per row: ~10 % of the instructions)
 // RES: a skip-connection gradient is added to dx (compile time: its two loads per row ride in the prefetch ring -- loaded on
@@ -512,53 +477,11 @@ __global__ __launch_bounds__(NTH) T3D_DWB_OCC void dw3_bwd2_kernel(const Dw3BArg
 }
 
 template <typename T, int CH>
-int launch_s1c(Dw3BArgs& a, hipStream_t st) {
+int launch_s1c(Dw3BArgs& a, const DwWalkPlan& plan, hipStream_t st) {
   constexpr int PF = 3;
-  const int CG = a.C / CH;
-  const int Wcols = (a.W + 1) / 2;     // column pairs
-  const long long per_row_chunk = (long long)a.B * Wcols * CG;
-  int nchunks = (int)((256LL * 64 * 24 + per_row_chunk - 1) / per_row_chunk);
-  int max_chunks = a.H / 8;
-  if (max_chunks < 1) max_chunks = 1;
-  if (nchunks > max_chunks) nchunks = max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  a.rows_per_chunk = cdiv(a.H, nchunks);
-  a.nchunks = cdiv(a.H, a.rows_per_chunk);
-  dim3 grid;
-  // tools/sweep_dwb.sh: the 4-channel variant needs AGPR spill space (1 wave/SIMD) and is best with one block per CU;
-  // the 2-channel variant fits 2 waves/SIMD and is best with two (every extra block is one more flush)
-  const int target_blocks = CH == 2 ? 512 : 256;
-  a.nrep = g_t3d_reduce.nrep;
-  a.rstride = g_t3d_reduce.stats_stride;
-  const int nth = 256;   // 512-thread blocks measured 4-5x slower (register budget)
-  // slab mapping (a wave = 64 consecutive channel groups of one column) only when it wastes < 12 % of the lanes
-  // (12 %: 14x14x576 -- 288 channel pairs, 5 slabs -- is 5 % faster in slabs than flattened, where every workgroup flushes
-  // sums of up to 512 channels instead of 128)
-  const int waste_pct = 12;
-  const bool flat = CG < 64 || (cdiv(CG, 64) * 64 - CG) * 100 > waste_pct * cdiv(CG, 64) * 64;
-  if (flat) {
-    a.slab = 0;
-    a.nitems = a.B * a.nchunks;
-    const int jb = cdiv(Wcols * CG, nth);
-    int gy = target_blocks / jb;
-    if (gy > a.nitems) gy = a.nitems;
-    if (gy < 1) gy = 1;
-    grid = dim3(jb, gy);
-  } else {
-    a.slab = 1;
-    a.nitems = Wcols * a.B * a.nchunks;
-    const int ns = cdiv(CG, 64);
-    int gx = target_blocks / ns;
-    if (gx > cdiv(a.nitems, nth / 64)) gx = cdiv(a.nitems, nth / 64);
-    if (gx < 1) gx = 1;
-    grid = dim3(gx, ns);
-  }
-  {   // depthwise weight gradient: one slot per workgroup when the caller provides enough of them (t3d_set_dw_slots)
-    const int needed = a.slab ? (int)grid.x : (int)(grid.x * grid.y);
-    a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
-    a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
-  }
-  const size_t lds = (size_t)22 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64 reduction scratch (before it: [9][Cb] weights, [3][Cb] derived coefficients)
+  const dim3 grid = dw_apply_plan(a, plan);
+  dw_take_slots(a, plan.slots_needed);
+  const size_t lds = plan.lds;
   // a pending BatchNorm-backward finalize of this launch's shared gradient coefficients is derived in the kernel's prologue
   a.fold = a.per_sample ? nullptr : t3d_take_fold(a.alpha);
   // (forcing 3-4 waves/SIMD through launch bounds spills to scratch: 3-7x slower)
@@ -579,12 +502,11 @@ int launch_s1c(Dw3BArgs& a, hipStream_t st) {
   return T3D_OK;
 }
 
+// 2 channels per thread wherever C allows (dwconv_walk.h: dw_row3_bwd_s1_spec)
 template <typename T>
-int launch_s1(Dw3BArgs& a, hipStream_t st) {
-  // 2 channels per thread: half the live registers (no AGPR spills, twice the resident waves) beats the wider
-  // loads of 4 channels per thread by 5-30 % on every layer
-  const int ch = 2;
-  return (ch == 2 && a.C % 2 == 0) ? launch_s1c<T, 2>(a, st) : launch_s1c<T, 4>(a, st);
+int launch_s1(Dw3BArgs& a, const DwShape& s, hipStream_t st) {
+  const DwWalkPlan plan = dw_walk_plan(s.B, s.C, dw_row3_bwd_s1_spec(s));
+  return plan.variant == 2 ? launch_s1c<T, 2>(a, plan, st) : launch_s1c<T, 4>(a, plan, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -895,45 +817,12 @@ __global__ __launch_bounds__(NTH) void dw3_bwd_s2_kernel(const Dw3BArgs a) {
 }
 
 template <typename T>
-int launch_s2(Dw3BArgs& a, hipStream_t st) {
-  constexpr int CH = 4, PF = 3;
-  const int CG = a.C / CH, Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
-  const long long per_row_chunk = (long long)a.B * Wo * CG;
-  int nchunks = (int)((256LL * 64 * 24 + per_row_chunk - 1) / per_row_chunk);
-  int max_chunks = Ho / 4;
-  if (max_chunks < 1) max_chunks = 1;
-  if (nchunks > max_chunks) nchunks = max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  a.rows_per_chunk = cdiv(Ho, nchunks);
-  a.nchunks = cdiv(Ho, a.rows_per_chunk);
-  dim3 grid;
-  const int target_blocks = 512;   // (round 4 sweep: 14x14x576 46.6 -> 41.4 us, 28x28x192 54.3 -> 51.5 against 384)
-  a.nrep = g_t3d_reduce.nrep;
-  a.rstride = g_t3d_reduce.stats_stride;
-  const int nth = 256;
-  if (CG < 64) {
-    a.slab = 0;
-    a.nitems = a.B * a.nchunks;
-    const int jb = cdiv(Wo * CG, nth);
-    int gy = target_blocks / jb;
-    if (gy > a.nitems) gy = a.nitems;
-    if (gy < 1) gy = 1;
-    grid = dim3(jb, gy);
-  } else {
-    a.slab = 1;
-    a.nitems = Wo * a.B * a.nchunks;
-    const int ns = cdiv(CG, 64);
-    int gx = target_blocks / ns;
-    if (gx > cdiv(a.nitems, nth / 64)) gx = cdiv(a.nitems, nth / 64);
-    if (gx < 1) gx = 1;
-    grid = dim3(gx, ns);
-  }
-  {   // depthwise weight gradient: one slot per workgroup when the caller provides enough of them (t3d_set_dw_slots)
-    const int needed = a.slab ? (int)grid.x : (int)(grid.x * grid.y);
-    a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
-    a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
-  }
-  const size_t lds = (size_t)22 * (a.slab ? 64 * CH : a.C) * sizeof(float);   // [11][Cb] fp64
+int launch_s2(Dw3BArgs& a, const DwShape& s, hipStream_t st) {
+  constexpr int PF = 3;
+  const DwWalkPlan plan = dw_walk_plan(s.B, s.C, dw_row3_bwd_s2_spec(s));
+  const dim3 grid = dw_apply_plan(a, plan);
+  dw_take_slots(a, plan.slots_needed);
+  const size_t lds = plan.lds;
   a.fold = a.per_sample ? nullptr : t3d_take_fold(a.alpha);
   switch (a.act) {
     case T3D_ACT_RELU: T3D_LAUNCH_TIMED((dw3_bwd_s2_kernel<T, PF, 256, T3D_ACT_RELU>), grid, dim3(256), lds, st, a); break;
@@ -957,11 +846,7 @@ int t3d_dw_row3_bwd(const DwShape& s, const void* dz, const void* y, const t3d_b
                     const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, hipStream_t st) {
   if (!t3d_dw_row3_bwd_can(s)) return T3D_ERR_ARG;
   Dw3BArgs a{};
-  a.dz = dz; a.y = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;
-  a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
-  if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
-  a.stats = stats; a.dw = dw;
-  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
-  if (s.stride == 2) return s.dtype == T3D_F32 ? launch_s2<float>(a, st) : launch_s2<bf16_t>(a, st);
-  return s.dtype == T3D_F32 ? launch_s1<float>(a, st) : launch_s1<bf16_t>(a, st);
+  dw_fill_bwd(a, s, dz, y, bb, w, x, pro, residual, dx, stats, dw);
+  if (s.stride == 2) return s.dtype == T3D_F32 ? launch_s2<float>(a, s, st) : launch_s2<bf16_t>(a, s, st);
+  return s.dtype == T3D_F32 ? launch_s1<float>(a, s, st) : launch_s1<bf16_t>(a, s, st);
 }

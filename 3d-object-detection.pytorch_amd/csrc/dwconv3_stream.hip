@@ -15,7 +15,7 @@
 //     for its whole chunk, meet in LDS once per block and leave as one fp64 atomic per channel.
 // The 9 x 8 weights of the thread's channels live in registers for the whole walk.
 #include <cstdlib>
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -36,26 +36,6 @@ struct Dw3Args {
   const T3dFold* fold;    // requested BatchNorm finalize of the INPUT's coefficients, derived in the prologue (common.h)
 };
 
-template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
-
-// raw buffer loads / stores: scalar descriptor + 32-bit scalar row offset + 32-bit lane offset -- no 64-bit vector address
-// arithmetic in the row loop (20 v_lshl_add_u64 + 8 v_mul_lo_u32 per three rows of the s=1 forward before); an offset beyond
-// num_records reads zeros / drops the store, which also replaces the store predicates of edge lanes
-template <typename RV>
-__device__ __forceinline__ RV bufload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  if constexpr (sizeof(RV) == 4) return __builtin_bit_cast(RV, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-  else if constexpr (sizeof(RV) == 8) return __builtin_bit_cast(RV, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-  else return __builtin_bit_cast(RV, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-template <typename RV>
-__device__ __forceinline__ void bufstore(const RV& v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  if constexpr (sizeof(RV) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-  else if constexpr (sizeof(RV) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, 0);
-  else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-}
-
 // raw vector -> activated fp32.  Zero padding applies to the ACTIVATED tensor: taps outside the image are removed by
 // zeroing the WEIGHTS of an out-of-image column (per item) and by skipping out-of-image rows (wave-uniform).
 template <typename T, int CH>
@@ -64,16 +44,6 @@ __device__ __forceinline__ void activate(const rawvec<T, CH>& r, const float* sc
 #pragma unroll
   for (int i = 0; i < CH; ++i) v[i] = (float)r[i];
   if (affine) act_affine_vec<CH>(v, sc, sh, act);
-}
-
-// ReLU6 of a BatchNorm affine in ONE packed instruction (bf16 storage): relu6(s x + t) = 6 clamp01((s/6) x + t/6), and
-// v_pk_fma_f32 takes the clamp modifier (result clamped to [0, 1] per half; probed on the box, tools/scratch/pkclamp.hip).
-// The caller scales (s, t) by 1/6 once per thread and folds the 6 into whatever multiplies the activated value next (the
-// stencil weights): two v_med3_f32 per channel pair leave the row loop.  fp32 storage keeps the exact form.
-__device__ __forceinline__ f32x2 pk_fma_clamp01(f32x2 a, f32x2 b, f32x2 c) {
-  f32x2 d;
-  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
 }
 
 // rounded store of one output vector + its BatchNorm sums, packed (two channels per v_pk_add / v_pk_fma)
@@ -585,51 +555,17 @@ __global__ __launch_bounds__(256) void dw3_fwd2_kernel(const Dw3Args a) {
 }
 
 template <typename T>
-int launch(Dw3Args& a, int s, hipStream_t st) {
+int launch(Dw3Args& a, const DwShape& s, hipStream_t st) {
   constexpr int PF = 3, CH = 4;
-  const int CG = a.C / CH;
   // row chunks: enough work items to fill the chip (several resident waves per SIMD), but long enough that
-  // the 1-2 halo rows re-read per chunk stay a small fraction
-  const long long per_row_chunk = (long long)a.B * a.Wo * CG;
-  int nchunks = (int)((256LL * 64 * 40 + per_row_chunk - 1) / per_row_chunk);
-  int max_chunks = a.Ho / 8;
-  if (max_chunks < 1) max_chunks = 1;
-  if (nchunks > max_chunks) nchunks = max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  a.rows_per_chunk = cdiv(a.Ho, nchunks);
-  a.nchunks = cdiv(a.Ho, a.rows_per_chunk);
+  // the 1-2 halo rows re-read per chunk stay a small fraction (dwconv_walk.h: dw_row3_fwd_spec)
+  const DwWalkPlan plan = dw_walk_plan(s.B, s.C, dw_row3_fwd_spec(s));
+  const dim3 grid = dw_apply_plan(a, plan);
+  const size_t lds = plan.lds;
   // (the two-column kernel addresses through 32-bit buffer offsets: tensors below 2 GB)
-  const bool use2 = (s == 1 && (size_t)a.B * a.H * a.W * a.C * sizeof(T) < (1ull << 31));
-  const int Wcols = use2 ? (a.Wo + 1) / 2 : a.Wo;     // work items per row: column pairs or columns
-  dim3 grid;
-  // persistent blocks: enough to fill the chip, few enough that the per-block flush stays cheap (tools/sweep_dwf.sh)
-  // (round 4 sweep: the small-spatial s=1 layers gain 4-5 % at 768: 28x28x192 38.0 -> 35.7 us, 14x14x384 24.8 -> 23.7)
-  const int target_blocks = (s == 1 && a.H > 28) ? 512 : 768;
-  a.nrep = g_t3d_reduce.nrep;
-  a.rstride = g_t3d_reduce.stats_stride;
-  if (CG < 64) {
-    a.slab = 0;
-    a.nitems = a.B * a.nchunks;
-    const int jb = cdiv(Wcols * CG, 256);
-    int gy = target_blocks / jb;
-    if (gy > a.nitems) gy = a.nitems;
-    if (gy < 1) gy = 1;
-    grid = dim3(jb, gy);
-  } else {
-    a.slab = 1;
-    a.nitems = Wcols * a.B * a.nchunks;
-    const int ns = cdiv(CG, 64);
-    int gx = target_blocks / ns;
-    if (gx > cdiv(a.nitems, 4)) gx = cdiv(a.nitems, 4);
-    if (gx < 1) gx = 1;
-    grid = dim3(gx, ns);
-  }
-  const size_t lds = (size_t)2 * a.C * sizeof(double);
+  const bool use2 = dw_row3_fwd_pairs(s);
   a.fold = t3d_take_fold(a.scale);
-  // (throughput mode only: in fp32 storage the sums' order noise stays at 1e-6 of the outputs and the grid would be one more
-  // perturbation between the parity mode and the reference)
-  a.quant = (a.stats && std::is_same<T, bf16_t>::value && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for((long long)a.B * a.Ho * a.Wo)
-                                                                                  : T3dQuant{0.0, 0.0};
+  a.quant = dw_quant<T>(a.stats, (long long)a.B * a.Ho * a.Wo);
   if (use2) {
     switch (a.act) {
       case T3D_ACT_RELU: T3D_LAUNCH_TIMED((dw3_fwd2_kernel<T, PF, T3D_ACT_RELU>), grid, dim3(256), lds, st, a); break;
@@ -647,7 +583,7 @@ int launch(Dw3Args& a, int s, hipStream_t st) {
     case T3D_ACT_HSWISH: T3D_DWF(SV, T3D_ACT_HSWISH); break;   \
     default: T3D_DWF(SV, T3D_ACT_NONE); break;                 \
   }
-    if (s == 1) { T3D_DWF_S(1) } else { T3D_DWF_S(2) }
+    if (s.stride == 1) { T3D_DWF_S(1) } else { T3D_DWF_S(2) }
 #undef T3D_DWF_S
 #undef T3D_DWF
   }
@@ -672,7 +608,7 @@ int t3d_dw_row3_fwd(const DwShape& s, const void* x, const t3d_prologue* pro, co
   a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
   a.Ho = (s.H + 2 - 3) / s.stride + 1;
   a.Wo = (s.W + 2 - 3) / s.stride + 1;
-  if (s.dtype == T3D_F32) return launch<float>(a, s.stride, st);
-  if (s.dtype == T3D_BF16) return launch<bf16_t>(a, s.stride, st);
-  return launch<f16_t>(a, s.stride, st);
+  if (s.dtype == T3D_F32) return launch<float>(a, s, st);
+  if (s.dtype == T3D_BF16) return launch<bf16_t>(a, s, st);
+  return launch<f16_t>(a, s, st);
 }

@@ -9,7 +9,7 @@
 // (oh, ow) and every pair belongs to exactly one thread: 25 + 25 packed FMAs per four input pixels, the full-resolution
 // x read once, dx written once, the quarter-resolution dz / y read three times (neighbour columns; L1 / L2).
 #include <cstdlib>
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -30,8 +30,6 @@ struct Dw5BArgs {
   int dw_slots;  // > 0: the weight gradient goes to one slot per workgroup (t3d_set_dw_slots; common.h: t3d_dw_flush)
   int* dw_used;
 };
-
-template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
 
 template <typename T, int PF>
 __global__ __launch_bounds__(256) void dw5_bwd_s2_kernel(const Dw5BArgs a) {
@@ -407,96 +405,24 @@ __global__ __launch_bounds__(256) void dw5_bwd_s1_kernel(const Dw5BArgs a) {
   }
 }
 
+// (dwconv_walk.h: dw_rowk_bwd_s1_spec / dw_rowk_bwd_s2_spec -- the reduction scratch always fits LDS)
 template <typename T>
-int launch5_s1(Dw5BArgs& a, hipStream_t st) {
-  constexpr int CH = 2;
-  const int CG = a.C / CH;
-  const long long per_row_chunk = (long long)a.B * a.W * CG;
-  int nchunks = (int)((256LL * 64 * 24 + per_row_chunk - 1) / per_row_chunk);
-  int max_chunks = a.H / 5;                   // every chunk re-reads 4 halo rows of the gradient
-  if (max_chunks < 1) max_chunks = 1;
-  if (nchunks > max_chunks) nchunks = max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  a.rows_per_chunk = cdiv(a.H, nchunks);
-  a.nchunks = cdiv(a.H, a.rows_per_chunk);
-  const int target_blocks = 512;
-  a.nrep = g_t3d_reduce.nrep;
-  a.rstride = g_t3d_reduce.stats_stride;
-  dim3 grid;
-  bool flat = CG < 64 || (cdiv(CG, 64) * 64 - CG) * 100 > 8 * cdiv(CG, 64) * 64;
-  if (flat && CG >= 64 && (size_t)54 * a.C * sizeof(float) > 64 * 1024) flat = false;   // the reduction scratch must fit LDS
-  if (flat) {
-    a.slab = 0;
-    a.nitems = a.B * a.nchunks;
-    const int jb = cdiv(a.W * CG, 256);
-    int gy = target_blocks / jb;
-    if (gy > a.nitems) gy = a.nitems;
-    if (gy < 1) gy = 1;
-    grid = dim3(jb, gy);
-  } else {
-    a.slab = 1;
-    a.nitems = a.W * a.B * a.nchunks;
-    const int ns = cdiv(CG, 64);
-    int gx = target_blocks / ns;
-    if (gx > cdiv(a.nitems, 4)) gx = cdiv(a.nitems, 4);
-    if (gx < 1) gx = 1;
-    grid = dim3(gx, ns);
-  }
-  {   // depthwise weight gradient: one slot per workgroup when the caller provides enough of them (t3d_set_dw_slots)
-    const int needed = a.slab ? (int)grid.x : (int)(grid.x * grid.y);
-    a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
-    a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
-  }
-  // [27][Cb] fp64: 27 KB for a slab; the flat mapping has fewer than 128 channels or was just checked to fit
-  const size_t lds = (size_t)54 * (a.slab ? 64 * CH : a.C) * sizeof(float);
-  T3D_LAUNCH_TIMED((dw5_bwd_s1_kernel<T>), grid, dim3(256), lds, st, a);
+int launch5_s1(Dw5BArgs& a, const DwShape& s, hipStream_t st) {
+  const DwWalkPlan plan = dw_walk_plan(s.B, s.C, dw_rowk_bwd_s1_spec(s));
+  const dim3 grid = dw_apply_plan(a, plan);
+  dw_take_slots(a, plan.slots_needed);
+  T3D_LAUNCH_TIMED((dw5_bwd_s1_kernel<T>), grid, dim3(256), plan.lds, st, a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 template <typename T>
-int launch5_s2(Dw5BArgs& a, hipStream_t st) {
-  constexpr int CH = 2, PF = 3;
-  const int CG = a.C / CH, Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
-  const long long per_row_chunk = (long long)a.B * Wo * CG;
-  int nchunks = (int)((256LL * 64 * 24 + per_row_chunk - 1) / per_row_chunk);
-  int max_chunks = Ho / 4;
-  if (max_chunks < 1) max_chunks = 1;
-  if (nchunks > max_chunks) nchunks = max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  a.rows_per_chunk = cdiv(Ho, nchunks);
-  a.nchunks = cdiv(Ho, a.rows_per_chunk);
-  const int target_blocks = 512;
-  a.nrep = g_t3d_reduce.nrep;
-  a.rstride = g_t3d_reduce.stats_stride;
-  dim3 grid;
-  bool flat = CG < 64 || (cdiv(CG, 64) * 64 - CG) * 100 > 8 * cdiv(CG, 64) * 64;
-  if (flat && CG >= 64 && (size_t)54 * a.C * sizeof(float) > 64 * 1024) flat = false;   // the reduction scratch must fit LDS
-  if (flat) {
-    a.slab = 0;
-    a.nitems = a.B * a.nchunks;
-    const int jb = cdiv(Wo * CG, 256);
-    int gy = target_blocks / jb;
-    if (gy > a.nitems) gy = a.nitems;
-    if (gy < 1) gy = 1;
-    grid = dim3(jb, gy);
-  } else {
-    a.slab = 1;
-    a.nitems = Wo * a.B * a.nchunks;
-    const int ns = cdiv(CG, 64);
-    int gx = target_blocks / ns;
-    if (gx > cdiv(a.nitems, 4)) gx = cdiv(a.nitems, 4);
-    if (gx < 1) gx = 1;
-    grid = dim3(gx, ns);
-  }
-  {   // depthwise weight gradient: one slot per workgroup when the caller provides enough of them (t3d_set_dw_slots)
-    const int needed = a.slab ? (int)grid.x : (int)(grid.x * grid.y);
-    a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= needed) ? needed : 0;
-    a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
-  }
-  // [27][Cb] fp64: 27 KB for a slab; the flat mapping has fewer than 128 channels or was just checked to fit
-  const size_t lds = (size_t)54 * (a.slab ? 64 * CH : a.C) * sizeof(float);
-  T3D_LAUNCH_TIMED((dw5_bwd_s2_kernel<T, PF>), grid, dim3(256), lds, st, a);
+int launch5_s2(Dw5BArgs& a, const DwShape& s, hipStream_t st) {
+  constexpr int PF = 3;
+  const DwWalkPlan plan = dw_walk_plan(s.B, s.C, dw_rowk_bwd_s2_spec(s));
+  const dim3 grid = dw_apply_plan(a, plan);
+  dw_take_slots(a, plan.slots_needed);
+  T3D_LAUNCH_TIMED((dw5_bwd_s2_kernel<T, PF>), grid, dim3(256), plan.lds, st, a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
@@ -510,11 +436,7 @@ int t3d_dw_rowk_bwd(const DwShape& s, const void* dz, const void* y, const t3d_b
                     const t3d_prologue* pro, const void* residual, void* dx, double* stats, float* dw, hipStream_t st) {
   if (!t3d_dw_rowk_bwd_can(s)) return T3D_ERR_ARG;
   Dw5BArgs a{};
-  a.dz = dz; a.y = y; a.x = x; a.res = residual; a.dx = dx; a.w = w;
-  a.alpha = bb->alpha; a.beta = bb->beta; a.gamma = bb->gamma; a.per_sample = bb->per_sample;
-  if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
-  a.stats = stats; a.dw = dw;
-  a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
-  if (s.dtype == T3D_F32) return s.stride == 2 ? launch5_s2<float>(a, st) : launch5_s1<float>(a, st);
-  return s.stride == 2 ? launch5_s2<bf16_t>(a, st) : launch5_s1<bf16_t>(a, st);
+  dw_fill_bwd(a, s, dz, y, bb, w, x, pro, residual, dx, stats, dw);
+  if (s.dtype == T3D_F32) return s.stride == 2 ? launch5_s2<float>(a, s, st) : launch5_s1<float>(a, s, st);
+  return s.stride == 2 ? launch5_s2<bf16_t>(a, s, st) : launch5_s1<bf16_t>(a, s, st);
 }

@@ -13,7 +13,7 @@
 // accumulators (100): one wave per SIMD with the accumulator file as spill space, like dw5_bwd_s1_kernel.
 #include <cstdlib>
 #include <type_traits>
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -37,32 +37,6 @@ struct P7Args {
   int* dw_used;
 };
 
-template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
-
-// A channel pair as it lies in memory, kept OPAQUE until the point of use: held as a vector of two bf16 the compiler widened
-// every loaded pair to two fp32 registers at once (the backward then wanted ~480 registers for three 49-pixel planes).
-template <typename T> struct Pair;
-template <> struct Pair<bf16_t> {
-  typedef unsigned int raw;
-  static __device__ __forceinline__ raw load(const bf16_t* p) { return *reinterpret_cast<const unsigned int*>(p); }
-  static __device__ __forceinline__ f32x2 widen(raw v) { return f32x2{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)}; }
-  static __device__ __forceinline__ void opaque(raw& v) { asm volatile("" : "+v"(v)); }
-};
-template <> struct Pair<float> {
-  typedef f32x2 raw;
-  static __device__ __forceinline__ raw load(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
-  static __device__ __forceinline__ f32x2 widen(raw v) { return v; }
-  static __device__ __forceinline__ void opaque(raw& v) { asm volatile("" : "+v"(v)); }
-};
-
-// weights of the workgroup's channel slab -> LDS [25][SLAB] (tap-major: a lane reads its channel pair as one 8-byte word)
-__device__ __forceinline__ void stage_weights(float* wl, const float* __restrict__ w, int cbase, int Cb) {
-  for (int i = threadIdx.x; i < 25 * Cb; i += 256) {
-    const int cl = i / 25, t = i - cl * 25;
-    wl[t * SLAB + cl] = w[(size_t)cbase * 25 + i];
-  }
-}
-
 template <typename T, int ACT>
 __global__ __launch_bounds__(256) void dw5_plane7_fwd_kernel(const P7Args a) {
   constexpr int CH = 2;
@@ -73,7 +47,7 @@ __global__ __launch_bounds__(256) void dw5_plane7_fwd_kernel(const P7Args a) {
   const int cbase = blockIdx.y * SLAB, Cb = min(SLAB, a.C - cbase);
   const bool on = 2 * lane < Cb;
   const int c0 = cbase + (on ? 2 * lane : 0);
-  stage_weights(wl, a.w, cbase, Cb);
+  stage_weights<25, SLAB>(wl, a.w, cbase, Cb);
   for (int i = threadIdx.x; i < 2 * SLAB; i += 256) lstat[i] = 0.0;
   __syncthreads();
   f32x2 wt[25];
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(256) void dw5_plane7_bwd_kernel(const P7Args a) {
   const int cbase = blockIdx.y * SLAB, Cb = min(SLAB, a.C - cbase);
   const bool on = 2 * lane < Cb;
   const int c0 = cbase + (on ? 2 * lane : 0);
-  stage_weights(wl, a.w, cbase, Cb);
+  stage_weights<25, SLAB>(wl, a.w, cbase, Cb);
   for (int i = threadIdx.x; i < 27 * Cb; i += 256) lacc[i] = 0.0;
   __syncthreads();
   f32x2 wt[25], wacc[25];
@@ -289,7 +263,7 @@ int launch_fwd(P7Args& a, int act, hipStream_t st) {
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   if (a.stats && a.nrep < 1) { a.nrep = 1; a.rstride = 0; }
-  a.quant = (a.stats && std::is_same<T, bf16_t>::value && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for((long long)a.B * NP) : T3dQuant{0.0, 0.0};
+  a.quant = dw_quant<T>(a.stats, (long long)a.B * NP);
   switch (act) {
     case T3D_ACT_RELU: T3D_LAUNCH_TIMED((dw5_plane7_fwd_kernel<T, T3D_ACT_RELU>), grid, dim3(256), 0, st, a); break;
     case T3D_ACT_RELU6: T3D_LAUNCH_TIMED((dw5_plane7_fwd_kernel<T, T3D_ACT_RELU6>), grid, dim3(256), 0, st, a); break;
@@ -307,8 +281,7 @@ int launch_bwd(P7Args& a, int act, hipStream_t st) {
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   if (a.nrep < 1) { a.nrep = 1; a.rstride = 0; }
-  a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= (int)grid.x) ? (int)grid.x : 0;
-  a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
+  dw_take_slots(a, (int)grid.x);
   const size_t lds = (size_t)25 * SLAB * sizeof(float) + (size_t)27 * SLAB * sizeof(double);
   switch (act) {
     case T3D_ACT_RELU: T3D_LAUNCH_TIMED((dw5_plane7_bwd_kernel<T, T3D_ACT_RELU>), grid, dim3(256), lds, st, a); break;

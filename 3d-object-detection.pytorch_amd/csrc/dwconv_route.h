@@ -5,6 +5,7 @@
 //   wanted: where it measured faster than the families behind it, with the timing table beside it.  Only the register
 //           tiles have planes they can take and lose on; every other family is wanted wherever it can.
 // A launcher called with a shape its `can` rejects returns T3D_ERR_ARG: it never answers "try the next one".
+// What the kernel files share below the dispatch -- device helpers, the row-walk launch planner -- is dwconv_walk.h.
 #pragma once
 #include "common.h"
 

@@ -1,6 +1,6 @@
 // Depthwise convolution entry points: validate, pick the kernel family ONCE by a pure function of the call's shape, settle
 // the pending BatchNorm finalize, launch (dwconv_route.h).  Host code only.
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -34,6 +34,21 @@ int t3d_dw_route(const DwShape& s) {
 extern "C" int t3d_dwconv_route(int backward, int dtype, int gated_input, int pooled, int B, int H, int W, int C, int k,
                                 int stride) {
   return t3d_dw_route(DwShape{backward != 0, dtype, gated_input != 0, pooled != 0 && !backward, B, H, W, C, k, stride});
+}
+
+// the launch geometry of a row-walk call, from the spec functions its launcher calls (dwconv_walk.h); zeros for the other families
+extern "C" int t3d_dwconv_plan(int backward, int dtype, int gated_input, int pooled, int B, int H, int W, int C, int k,
+                               int stride, int* out) {
+  if (!out) return T3D_ERR_ARG;
+  const DwShape s{backward != 0, dtype, gated_input != 0, pooled != 0 && !backward, B, H, W, C, k, stride};
+  const int route = t3d_dw_route(s);
+  for (int i = 0; i < 9; ++i) out[i] = 0;
+  if (route == T3D_DW_ROW3 || route == T3D_DW_ROWK) {
+    const DwWalkPlan p = dw_walk_plan(s.B, s.C, dw_walk_spec(route, s));
+    const int v[9] = {p.rows_per_chunk, p.nchunks, p.slab, p.nitems, (int)p.gx, (int)p.gy, p.slots_needed, (int)p.lds, p.variant};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+  }
+  return route;
 }
 
 extern "C" int t3d_dwconv_force_route(int route) {

@@ -13,7 +13,7 @@
 // data gradient first, weight gradient second (plane kernel's two phases, for the same register reason).
 #include <cstdlib>
 #include <type_traits>
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -38,29 +38,6 @@ struct TileArgs {
   int* dw_used;
 };
 
-template <typename T> struct Pair;
-template <> struct Pair<bf16_t> {
-  typedef unsigned int raw;
-  static __device__ __forceinline__ raw load(const bf16_t* p) { return *reinterpret_cast<const unsigned int*>(p); }
-  static __device__ __forceinline__ f32x2 widen(raw v) { return f32x2{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)}; }
-  static __device__ __forceinline__ void opaque(raw& v) { asm volatile("" : "+v"(v)); }
-};
-template <> struct Pair<float> {
-  typedef f32x2 raw;
-  static __device__ __forceinline__ raw load(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
-  static __device__ __forceinline__ f32x2 widen(raw v) { return v; }
-  static __device__ __forceinline__ void opaque(raw& v) { asm volatile("" : "+v"(v)); }
-};
-template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
-
-template <int K2>
-__device__ __forceinline__ void stage_weights(float* wl, const float* __restrict__ w, int cbase, int Cb) {
-  for (int i = threadIdx.x; i < K2 * Cb; i += 256) {
-    const int cl = i / K2, t = i - cl * K2;
-    wl[t * SLAB + cl] = w[(size_t)cbase * K2 + i];
-  }
-}
-
 template <typename T, int ACT, int K, int TH, int TW>
 __global__ __launch_bounds__(256) void dw5_tile_fwd_kernel(const TileArgs a) {
   constexpr int CH = 2, KK = K, PADK = K / 2, K2 = K * K, WH = TH + K - 1, WW = TW + K - 1;
@@ -71,7 +48,7 @@ __global__ __launch_bounds__(256) void dw5_tile_fwd_kernel(const TileArgs a) {
   const int cbase = blockIdx.y * SLAB, Cb = min(SLAB, a.C - cbase);
   const bool on = 2 * lane < Cb;
   const int c0 = cbase + (on ? 2 * lane : 0);
-  stage_weights<K2>(wl, a.w, cbase, Cb);
+  stage_weights<K2, SLAB>(wl, a.w, cbase, Cb);
   for (int i = threadIdx.x; i < 2 * SLAB; i += 256) lstat[i] = 0.0;
   __syncthreads();
   f32x2 wt[K2];
@@ -173,7 +150,7 @@ __global__ __launch_bounds__(256) void dw5_tile_bwd_kernel(const TileArgs a) {
   const int cbase = blockIdx.y * SLAB, Cb = min(SLAB, a.C - cbase);
   const bool on = 2 * lane < Cb;
   const int c0 = cbase + (on ? 2 * lane : 0);
-  stage_weights<K2>(wl, a.w, cbase, Cb);
+  stage_weights<K2, SLAB>(wl, a.w, cbase, Cb);
   for (int i = threadIdx.x; i < (K2 + 2) * Cb; i += 256) lacc[i] = 0.0;
   __syncthreads();
   f32x2 wt[K2], wacc[K2];
@@ -328,7 +305,7 @@ __global__ __launch_bounds__(256) void dw5_tile_fwd_s2_kernel(const TileArgs a) 
   const bool on = 2 * lane < Cb;
   const int c0 = cbase + (on ? 2 * lane : 0);
   const int Ho = (a.H + 2 * PADK - K) / 2 + 1, Wo = (a.W + 2 * PADK - K) / 2 + 1;
-  stage_weights<K2>(wl, a.w, cbase, Cb);
+  stage_weights<K2, SLAB>(wl, a.w, cbase, Cb);
   for (int i = threadIdx.x; i < 2 * SLAB; i += 256) lstat[i] = 0.0;
   __syncthreads();
   f32x2 wt[K2];
@@ -434,7 +411,7 @@ __global__ __launch_bounds__(256) void dw5_tile_bwd_s2_kernel(const TileArgs a) 
   const bool on = 2 * lane < Cb;
   const int c0 = cbase + (on ? 2 * lane : 0);
   const int Ho = (a.H + 2 * PADK - K) / 2 + 1, Wo = (a.W + 2 * PADK - K) / 2 + 1;
-  stage_weights<K2>(wl, a.w, cbase, Cb);
+  stage_weights<K2, SLAB>(wl, a.w, cbase, Cb);
   for (int i = threadIdx.x; i < (K2 + 2) * Cb; i += 256) lacc[i] = 0.0;
   __syncthreads();
   f32x2 wt[K2], wacc[K2];
@@ -609,7 +586,7 @@ int launch_fwd(TileArgs& a, int act, int stride, hipStream_t st) {
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   if (a.stats && a.nrep < 1) { a.nrep = 1; a.rstride = 0; }
-  a.quant = (a.stats && std::is_same<T, bf16_t>::value && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for((long long)a.B * Ho * Wo) : T3dQuant{0.0, 0.0};
+  a.quant = dw_quant<T>(a.stats, (long long)a.B * Ho * Wo);
   const size_t lds = 0;
   if (stride == 2) { T3D_TILE_ACT(dw5_tile_fwd_s2_kernel, K, S::F2H, S::F2W) }
   else { T3D_TILE_ACT(dw5_tile_fwd_kernel, K, S::FH, S::FW) }
@@ -627,8 +604,7 @@ int launch_bwd(TileArgs& a, int act, int stride, hipStream_t st) {
   a.nrep = g_t3d_reduce.nrep;
   a.rstride = g_t3d_reduce.stats_stride;
   if (a.nrep < 1) { a.nrep = 1; a.rstride = 0; }
-  a.dw_slots = (a.dw && g_t3d_reduce.dw_slots >= (int)grid.x) ? (int)grid.x : 0;
-  a.dw_used = a.dw ? g_t3d_reduce.dw_used : nullptr;
+  dw_take_slots(a, (int)grid.x);
   const size_t lds = (size_t)K * K * SLAB * sizeof(float) + (size_t)(K * K + 2) * SLAB * sizeof(double);
   if (stride == 2) { T3D_TILE_ACT(dw5_tile_bwd_s2_kernel, K, S::B2H, S::B2W) }
   else { T3D_TILE_ACT(dw5_tile_bwd_kernel, K, S::BH, S::BW) }

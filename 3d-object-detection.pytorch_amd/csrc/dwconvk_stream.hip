@@ -14,7 +14,7 @@
 // (wave-uniform); loads are unconditional from clamped addresses.
 #include <cstdlib>
 #include <type_traits>
-#include "dwconv_route.h"
+#include "dwconv_walk.h"
 
 namespace {
 
@@ -34,8 +34,6 @@ struct DwkArgs {
   long long rstride;
   T3dQuant quant;  // BatchNorm sums snapped onto a fixed grid: order-independent (common.h)
 };
-
-template <typename T, int CH> using rawvec = T __attribute__((ext_vector_type(CH)));
 
 constexpr int floormod(int a, int n) { return ((a % n) + n) % n; }
 constexpr int floordiv(int a, int n) { return (a - floormod(a, n)) / n; }
@@ -192,71 +190,32 @@ __global__ __launch_bounds__(256) void dwk_fwd_kernel(const DwkArgs a) {
 }
 
 template <typename T, int K, int S, int NC>
-int launch_nc(DwkArgs& a, hipStream_t st) {
-  constexpr int CH = 2;
-  const int CG = a.C / CH;
+int launch_nc(DwkArgs& a, const DwWalkPlan& plan, hipStream_t st) {
   a.Wb = cdiv(a.Wo, NC);
-  const long long per_row_chunk = (long long)a.B * a.Wb * CG;
-  // row chunks per image: enough (thread, item) pairs to fill the chip once (~1600 waves) and no more -- every chunk re-reads
-  // K - 1 halo rows and pays the ring fill again.  (Round 6, isolated at B = 256: 28x28x120 5x5 s1 with four columns per
-  // thread ran 79 us in three chunks, 58 in one; the 40-fold target dates from the one-column kernel.)
-  const long long want = (K == 5 && S == 1 && NC > 1) ? 256LL * 64 * 6 : 256LL * 64 * 40;
-  int nchunks = (int)((want + per_row_chunk - 1) / per_row_chunk);
-  int max_chunks = a.Ho / 8;
-  if (max_chunks < 1) max_chunks = 1;
-  if (nchunks > max_chunks) nchunks = max_chunks;
-  if (nchunks < 1) nchunks = 1;
-  a.rows_per_chunk = cdiv(a.Ho, nchunks);
-  a.nchunks = cdiv(a.Ho, a.rows_per_chunk);
-  const int target_blocks = (K == 5 && S == 1) ? 1024 : 768;
-  a.nrep = g_t3d_reduce.nrep;
-  a.rstride = g_t3d_reduce.stats_stride;
-  dim3 grid;
-  const bool flat = CG < 64 || (cdiv(CG, 64) * 64 - CG) * 100 > 8 * cdiv(CG, 64) * 64;
-  if (flat) {
-    a.slab = 0;
-    a.nitems = a.B * a.nchunks;
-    const int jb = cdiv(a.Wb * CG, 256);
-    int gy = target_blocks / jb;
-    if (gy > a.nitems) gy = a.nitems;
-    if (gy < 1) gy = 1;
-    grid = dim3(jb, gy);
-  } else {
-    a.slab = 1;
-    a.nitems = a.Wb * a.B * a.nchunks;
-    const int ns = cdiv(CG, 64);
-    int gx = target_blocks / ns;
-    if (gx > cdiv(a.nitems, 4)) gx = cdiv(a.nitems, 4);
-    if (gx < 1) gx = 1;
-    grid = dim3(gx, ns);
-  }
-  const size_t lds = (size_t)2 * (a.slab ? 64 * CH : a.C) * sizeof(double);
+  const dim3 grid = dw_apply_plan(a, plan);
   // (throughput mode only, as in dwconv3_stream.hip)
-  a.quant = (a.stats && std::is_same<T, bf16_t>::value && !T3D_ENV_SET("T3D_NO_SNAP")) ? t3d_quant_for((long long)a.B * a.Ho * a.Wo)
-                                                                                  : T3dQuant{0.0, 0.0};
-  T3D_LAUNCH_TIMED((dwk_fwd_kernel<T, K, S, NC>), grid, dim3(256), lds, st, a);
+  a.quant = dw_quant<T>(a.stats, (long long)a.B * a.Ho * a.Wo);
+  T3D_LAUNCH_TIMED((dwk_fwd_kernel<T, K, S, NC>), grid, dim3(256), plan.lds, st, a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
+// output columns per thread: four for stride 1 where the row has them, one for stride 2 (dwconv_walk.h: dw_rowk_fwd_spec)
 template <typename T, int K, int S>
-int launch_ks(DwkArgs& a, hipStream_t st) {
-  // output columns per thread, measured per layer of mobilenetv3_large at B = 256 (tools/scratch/time_dwk.py, us at NC = 1 / 2 / 4):
-  //   3x3 s1 14^2 x 480 / 672 (squeeze-excite): 62.6 / 50.1 / 49.2 and 77.9 / 61.4 / 57.3;  5x5 s1 28^2 x 120: 93.7 / 105.7 / 77.8,
-  //   7^2 x 960: 66.3 / 78.6 / 62.8;  5x5 s2 56^2 x 72: 93.1 / 95.3 (/ 93.8 at NC = 2), 14^2 x 672: 69.2 / 84.9 -- four columns for
-  //   stride 1, one for stride 2
+int launch_ks(DwkArgs& a, const DwShape& s, hipStream_t st) {
+  const DwWalkPlan plan = dw_walk_plan(s.B, s.C, dw_rowk_fwd_spec(s));
   if constexpr (S == 1) {
-    if (a.Wo >= 4) return launch_nc<T, K, S, 4>(a, st);
+    if (plan.variant == 4) return launch_nc<T, K, S, 4>(a, plan, st);
   }
-  return launch_nc<T, K, S, 1>(a, st);
+  return launch_nc<T, K, S, 1>(a, plan, st);
 }
 
 template <typename T>
-int launch_t(DwkArgs& a, int k, int s, hipStream_t st) {
-  if (k == 5 && s == 1) return launch_ks<T, 5, 1>(a, st);
-  if (k == 5 && s == 2) return launch_ks<T, 5, 2>(a, st);
-  if (k == 3 && s == 1) return launch_ks<T, 3, 1>(a, st);
-  return launch_ks<T, 3, 2>(a, st);
+int launch_t(DwkArgs& a, const DwShape& s, hipStream_t st) {
+  if (s.k == 5 && s.stride == 1) return launch_ks<T, 5, 1>(a, s, st);
+  if (s.k == 5 && s.stride == 2) return launch_ks<T, 5, 2>(a, s, st);
+  if (s.k == 3 && s.stride == 1) return launch_ks<T, 3, 1>(a, s, st);
+  return launch_ks<T, 3, 2>(a, s, st);
 }
 
 }  // namespace
@@ -274,10 +233,9 @@ int t3d_dw_rowk_fwd(const DwShape& s, const void* x, const t3d_prologue* pro, co
   a.x = x; a.y = y; a.w = w; a.stats = stats; a.gap = gap_sum; a.gapq = g_t3d_reduce.pool_exact;
   if (pro) { a.scale = pro->scale; a.shift = pro->shift; a.act = pro->act; }
   a.B = s.B; a.H = s.H; a.W = s.W; a.C = s.C;
-  const int pad = (s.k - 1) / 2;
-  a.Ho = (s.H + 2 * pad - s.k) / s.stride + 1;
-  a.Wo = (s.W + 2 * pad - s.k) / s.stride + 1;
-  if (s.dtype == T3D_F32) return launch_t<float>(a, s.k, s.stride, st);
-  if (s.dtype == T3D_BF16) return launch_t<bf16_t>(a, s.k, s.stride, st);
-  return launch_t<f16_t>(a, s.k, s.stride, st);
+  a.Ho = dw_out(s.H, s.k, s.stride);
+  a.Wo = dw_out(s.W, s.k, s.stride);
+  if (s.dtype == T3D_F32) return launch_t<float>(a, s, st);
+  if (s.dtype == T3D_BF16) return launch_t<bf16_t>(a, s, st);
+  return launch_t<f16_t>(a, s, st);
 }

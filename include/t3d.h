@@ -217,9 +217,16 @@ int t3d_dwconv_bwd(int dtype, const void* dz, const void* y, const t3d_bnbwd* bb
  * device call.  gated_input: a squeeze-excite gate in the input prologue (pro->se); pooled: gap_sum != NULL (forward only).
  * t3d_dwconv_force_route (tests and timing tools only; process-wide, T3D_DW_AUTO clears it): while a route is forced, the
  * query and both entry points take that family wherever its kernels are correct -- measured faster or not -- and return
- * T3D_ERR_UNSUPPORTED, launching nothing, where they are not. */
+ * T3D_ERR_UNSUPPORTED, launching nothing, where they are not.
+ * t3d_dwconv_plan returns what t3d_dwconv_route returns (a forced route included) and, for the two row-walk families, the
+ * launch geometry their launcher takes (csrc/dwconv_walk.h: one planner, six specs): out[0..8] = rows per chunk, chunks,
+ * slab mapping (0: flat), work items, grid.x, grid.y, weight-gradient slots needed, dynamic LDS bytes, template variant
+ * (channels per thread; output columns per thread for the T3D_DW_ROWK forward).  Zeros for every other route or an error.
+ * No device call. */
 enum { T3D_DW_AUTO = -1, T3D_DW_TILE = 0, T3D_DW_ROW3 = 1, T3D_DW_PLANE7 = 2, T3D_DW_ROWK = 3, T3D_DW_LDS = 4 };
 int t3d_dwconv_route(int backward, int dtype, int gated_input, int pooled, int B, int H, int W, int C, int k, int stride);
+int t3d_dwconv_plan(int backward, int dtype, int gated_input, int pooled, int B, int H, int W, int C, int k, int stride,
+                    int* out);
 int t3d_dwconv_force_route(int route);
 
 /* BatchNorm backward bookkeeping: from the reductions the gradient-producing kernel emitted,
