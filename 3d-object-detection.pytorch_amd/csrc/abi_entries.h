@@ -37,6 +37,8 @@
   Q(t3d_pwconv_bwd_yfree_scratch) Q(t3d_dwconv_route) Q(t3d_dwconv_plan) Q(t3d_dwconv_force_route) \
   Q(t3d_augment_crops_u8) Q(t3d_augment_resized_u8) Q(t3d_augment_chain_crops_u8) Q(t3d_augment_chain_resized_u8) \
   Q(t3d_detect_augment_u8) Q(t3d_detect_draw) Q(t3d_detect_draw_host) Q(t3d_jpeg_index) Q(t3d_jpeg_decode_work_bytes) Q(t3d_jpeg_decode_u8) Q(t3d_jpeg_decode_roi_u8) \
+  Q(t3d_detect_roi_plan) \
+  Q(t3d_detect_roi_plan_host) \
   Q(t3d_jpeg_header) Q(t3d_jpeg_index_work_bytes) Q(t3d_jpeg_index_device) \
   Q(t3d_jpeg_encode_setup)Q(t3d_jpeg_encode_work_bytes) Q(t3d_jpeg_encode_u8) \
   Q(t3d_ssd_multibox_work_bytes) Q(t3d_ssd_head_bwd_work_bytes) Q(t3d_track_state_bytes) Q(t3d_track_lds_bytes) \

@@ -106,7 +106,9 @@ def build_detection_loader(cfg):
     optional `data.cache` ('device': the files, their JPEG index and the annotations are kept in GPU memory and every batch is
     decoded, drawn and augmented there, dataloaders/detection_arena.py -- it implies the index, `data.decode_index` and
     `data.decode_seg_mcus` apply as for decode='device', `workers_per_gpu` is not used; any other value raises ValueError) with
-    its budget `data.cache_max_gb` (GiB, default 32: a set that does not fit raises before anything is allocated).
+    its budget `data.cache_max_gb` (GiB, default 32: a set that does not fit raises before anything is allocated); optional
+    `data.decode_crop` (default off; with `data.cache = 'device'` only, ValueError without it: the train loader decodes of every
+    frame only the part its drawn crop reads -- `ArenaDetectionLoader(crop_decode=True)` -- the same batches bit for bit).
     -> (train, val) `GpuDetectionLoader`s, or `ArenaDetectionLoader`s with `data.cache = 'device'` (the same tuples bit for bit,
     but G is the largest box count of the SET, not of the batch; each rank holds the whole arena):
     train yields (imgs uint8 [B,S,S,3], gt_boxes, gt_labels, gt_counts), shuffled by (seed, epoch), last partial batch dropped;
@@ -137,6 +139,10 @@ def build_detection_loader(cfg):
         raise ValueError(f"data.cache = {cache!r}: only 'device' (files, index and annotations kept in GPU memory) or nothing is built")
     if cache:
         decode = 'device'
+    decode_crop = bool(_get(data, 'decode_crop', False))
+    if decode_crop and not cache:
+        raise ValueError("data.decode_crop = True needs data.cache = 'device': only the arena loader, which draws the crops on the "
+                         'device before it decodes, can decode the drawn crop alone')
     stem, seg_mcus = _get(data, 'decode_index'), _get(data, 'decode_seg_mcus')
 
     def indexed(d, which):
@@ -155,7 +161,8 @@ def build_detection_loader(cfg):
         arenas = [DetectionArena(d, max_gb) for d in (ds, dv)]          # (both planned -- budget, box capacity -- before either is filled)
         for a in arenas:
             a.fill()
-        train = ArenaDetectionLoader(arenas[0], train_tf, bs, sampler=sampler, drop_last=True, seed=seed, rank=rk)
+        train = ArenaDetectionLoader(arenas[0], train_tf, bs, sampler=sampler, drop_last=True, seed=seed, rank=rk,
+                                     crop_decode=decode_crop)
         sub = torch.utils.data.Subset(dv, range(rk, len(dv), world)) if world > 1 else dv
         val = ArenaDetectionLoader(arenas[1], test_tf, bs, indices=range(rk, len(dv), world), seed=seed, rank=rk, dataset=sub)
         return train, val

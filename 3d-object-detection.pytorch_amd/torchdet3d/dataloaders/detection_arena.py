@@ -19,7 +19,10 @@ device-to-device copies of host-decoded frames (only files the index refused; no
 `t3d_detect_draw` (csrc/detect_draw.hip: the draws, the crop search, the boxes and the records, bit for bit those of
 `DetectionAugmentPipeline.draw` / `.boxes` / `.records` from the same key) and `t3d_detect_augment_u8`.  The test pipeline takes
 the same route without the draw: records with no flag, `t3d_augment_crops_u8`, boxes scaled and clipped in vectorised numpy,
-`ori_shapes` yielded.
+`ori_shapes` yielded.  With `crop_decode` (`data.decode_crop`, off by default) the train pipeline's order is upload,
+`t3d_detect_draw`, `t3d_detect_roi_plan` (csrc/detect_roi.hip: the drawn records -> the rectangle, item and rewritten record of
+every device-decoded frame, one launch, nothing read back), `t3d_jpeg_decode_roi_u8` with the host's whole-frame totals as its
+bounds, the copies, `t3d_detect_augment_u8`: only what a crop reads is decoded, and the batches are the same bit for bit.
 
 Yields what `GpuDetectionLoader` yields, bit for bit, with ONE difference: G, the second dimension of `gt_boxes` and
 `gt_labels`, is the ARENA's capacity -- the largest box count of any image of the set, at least 1 -- not the batch's largest
@@ -33,12 +36,12 @@ import numpy as np
 import torch
 
 from .detection import DET_SAMPLE_DTYPE, _CROP_TAG, resize_boxes
-from .jpeg import frame_blocks, item_table, launch_decode, starts
+from .jpeg import ITEM_DTYPE, frame_blocks, item_table, launch_decode, launch_decode_roi, starts
 from .objectron import resize_records
 from .staging import PinnedRing, StagedLoader, device_parts, upload
 
 __all__ = ['DetectionArena', 'ArenaDetectionLoader', 'plan_arena_batch', 'pipeline_cfg', 'key_words', 'detect_draw_host',
-           'DRAW_CFG_LEN', 'MAX_BOXES']
+           'detect_roi_plan_host', 'DRAW_CFG_LEN', 'MAX_BOXES']
 
 DRAW_CFG_LEN = 34           # include/t3d.h: cfg of t3d_detect_draw, by position
 MAX_BOXES = 64              # t3d_ssd_multibox_loss and t3d_detect_draw take no more boxes an image
@@ -106,6 +109,26 @@ def detect_draw_host(pipeline, key, frames, boxes, labels, box_start, G):
     return rec, gb, gl, gc, diag
 
 
+def detect_roi_plan_host(records, infos, items, src_bytes, sample=None):
+    """`t3d_detect_roi_plan_host`: from drawn records to the rectangle decode's tables on the CPU (no GPU is touched).  records
+    [B] DET_SAMPLE_DTYPE; infos [n] INFO_DTYPE and items [n] ITEM_DTYPE, the frames' index rows and whole-frame items; sample
+    int32 [n]: the record of each item (None: item j, record j).
+    -> (records rewritten (a copy), roi items [n] ITEM_DTYPE, rects int32 [n, 12], diag int32 [n, 2] = (pixels, blocks))."""
+    from .. import _native as N
+    rec = np.array(records, DET_SAMPLE_DTYPE).reshape(-1)
+    infos, items = np.ascontiguousarray(infos).reshape(-1), np.ascontiguousarray(items, ITEM_DTYPE).reshape(-1)
+    n = len(items)
+    if infos.dtype.itemsize != 864 or len(infos) != n:
+        raise ValueError('infos: one t3d_jpeg_info row an item')
+    sample = None if sample is None else np.ascontiguousarray(sample, np.int32).reshape(n)
+    out, rects, diag = np.zeros(n, ITEM_DTYPE), np.full((n, 12), -1, np.int32), np.full((n, 2), -7, np.int32)
+    rc = N.lib().t3d_detect_roi_plan_host(rec.ctypes.data, len(rec), None if sample is None else sample.ctypes.data, infos.ctypes.data,
+                                          items.ctypes.data, n, int(src_bytes), out.ctypes.data, rects.ctypes.data, diag.ctypes.data, None)
+    if rc != 0:
+        raise RuntimeError(f't3d_detect_roi_plan_host failed with code {rc}')
+    return rec, out, rects, diag
+
+
 def plan_arena_batch(idx, file_off, size, seg_start, h, w, blocks, nseg):
     """Pure numpy: the tables of one t3d_jpeg_decode_u8 call over RESIDENT files.  idx: the batch's dataset indices (files the
     device decodes); the other arguments are the arena's per-file host arrays.  -> dict(items [len(idx)] ITEM_DTYPE, frames int64
@@ -154,6 +177,10 @@ class DetectionArena:
         dev = self.kind == 0
         self.nseg = np.where(dev, infos['nseg'], 0).astype(np.int64)
         self.blocks = np.where(dev, frame_blocks(infos), 0)
+        # a whole frame's share of t3d_jpeg_decode_roi_u8's grid bounds: upper bounds of any rectangle's
+        per_row = (np.maximum(infos['mcus_x'].astype(np.int64), 1) - 1) // np.maximum(infos['seg_mcus'], 1) + 2
+        self.lanes = np.where(dev, infos['mcus_y'] * per_row, 0).astype(np.int64)
+        self.runs = np.where(dev, self.h * ((self.w + 3) // 4), 0).astype(np.int64)
         counts = np.array([len(l) for l in fr._labels], np.int64).reshape(-1)
         self.box_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.boxes = np.concatenate([np.asarray(b, np.float32).reshape(-1, 4) for b in fr._boxes] + [np.zeros((0, 4), np.float32)])
@@ -225,10 +252,14 @@ class DetectionArena:
 class ArenaDetectionLoader(StagedLoader):
     """Batches for the detector from a filled `DetectionArena` (the module's docstring): the tuples of `GpuDetectionLoader`, with
     G = `arena.G`.  indices: the dataset indices this loader walks, in order, when there is no sampler (None: all of them);
-    `dataset` is what `GpuDetectionLoader.dataset` would be (the frames, or the Subset of them)."""
+    `dataset` is what `GpuDetectionLoader.dataset` would be (the frames, or the Subset of them).
+    crop_decode (`data.decode_crop`): with a random pipeline the draw runs BEFORE the decode, `t3d_detect_roi_plan` turns its
+    records into rectangles on the device, and `t3d_jpeg_decode_roi_u8` decodes of every frame only what its crop reads; the
+    batches are the same bit for bit.  `last_crop_diag` then holds the batch's device int32 [n, 2]: pixels and 8x8 blocks asked
+    for, a row per device-decoded frame.  The test pipeline reads whole frames and ignores the flag."""
 
     def __init__(self, arena, pipeline, batch_size, sampler=None, indices=None, drop_last=False, seed=0, rank=0, prefetch=1,
-                 dataset=None):
+                 dataset=None, crop_decode=False):
         if arena.data is None:
             raise RuntimeError('ArenaDetectionLoader needs a filled arena: call DetectionArena.fill() first')
         super().__init__(prefetch, min_staging=1 << 14)
@@ -238,6 +269,7 @@ class ArenaDetectionLoader(StagedLoader):
         self.indices = np.arange(len(arena), dtype=np.int64) if indices is None else np.asarray(list(indices), np.int64)
         self.dataset = arena.frames if dataset is None else dataset
         self.decode, self.last_status = 'arena', None
+        self.crop_decode, self.last_crop_diag = bool(crop_decode), None
         self._cfg = pipeline_cfg(pipeline)
 
     def _order(self):
@@ -249,7 +281,8 @@ class ArenaDetectionLoader(StagedLoader):
 
     def host_plan(self, idx):
         """The host half of one batch, vectorised numpy only.  idx: the batch's dataset indices.  -> (parts: the uint8 arrays of
-        the one upload -- frames | items | gather indices [| records | boxes | labels | counts | shapes for the test pipeline] --
+        the one upload -- frames | items | gather indices [| records | boxes | labels | counts | shapes for the test pipeline]
+        [| batch positions of the device-decoded files with crop_decode] --
         plan of the device-decoded files, positions of the host-decoded frames)."""
         A = self.arena
         idx = np.asarray(idx, np.int64)
@@ -262,7 +295,10 @@ class ArenaDetectionLoader(StagedLoader):
         plan = plan_arena_batch(idx[on_dev], A.file_off, A.size, A.seg_start, A.h, A.w, A.blocks, A.nseg)
         plan['items']['out_offset'] = out_off[on_dev]
         plan['out_bytes'], plan['total_segs'] = int(nb.sum()), A.segs.numel() // 16
-        parts = [frames.reshape(-1).view(np.uint8), plan['items'].view(np.uint8), idx[on_dev].view(np.uint8)]
+        dev_idx = idx[on_dev]
+        plan['max_lanes'] = int(A.lanes[dev_idx].max()) if len(dev_idx) else 1
+        plan['max_runs'] = int(A.runs[dev_idx].max()) if len(dev_idx) else 1
+        parts = [frames.reshape(-1).view(np.uint8), plan['items'].view(np.uint8), dev_idx.view(np.uint8)]
         if not self.pipeline.random:
             G = A.G
             rec = resize_records(frames)
@@ -275,6 +311,8 @@ class ArenaDetectionLoader(StagedLoader):
             gl[row, col] = A.labels[src]
             parts += [rec.view(np.uint8), gb.reshape(-1).view(np.uint8), gl.reshape(-1).view(np.uint8), cnt.astype(np.int32).view(np.uint8),
                       np.stack([hh, ww], 1).astype(np.int32).reshape(-1).view(np.uint8)]
+        elif self.crop_decode:
+            parts.append(on_dev.astype(np.int32).view(np.uint8))
         return parts, plan, np.flatnonzero(A.kind[idx] != 0), frames
 
     def finish(self, idx, key_tail, prefetch=None):
@@ -297,27 +335,44 @@ class ArenaDetectionLoader(StagedLoader):
             imgs = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev)
             src = torch.empty(max(plan['out_bytes'], 1), dtype=torch.uint8, device=dev)
             n_dev = len(plan['items'])
-            if n_dev:
-                infos = A.infos.index_select(0, part(2, torch.int64, n_dev))
+            crop = self.crop_decode and self.pipeline.random
+            infos = A.infos.index_select(0, part(2, torch.int64, n_dev)) if n_dev else None
+            if crop:                               # the draw reads no pixel: it runs first and says what to decode
+                rec, gb, gl, gc = self._draw(part, B, key_tail, dev)
+                if n_dev:
+                    items, rects, diag = device_parts([n_dev * ITEM_DTYPE.itemsize, n_dev * 48, n_dev * 8], dev)
+                    N.call('t3d_detect_roi_plan', N.ptr(rec), B, N.ptr(part(3, torch.uint8, -1)), N.ptr(infos), N.ptr(part(1, torch.uint8, -1)),
+                           n_dev, src.numel(), N.ptr(items), N.ptr(rects), N.ptr(diag), N.stream())
+                    self.last_status = launch_decode_roi(A.data, infos, A.segs, items, rects, plan, src)
+                    self.last_crop_diag = diag.view(torch.int32).view(n_dev, 2)
+            elif n_dev:
                 self.last_status = launch_decode(A.data, infos, A.segs, part(1, torch.uint8, -1), plan, src)
-            else:
+            if not n_dev:
                 self.last_status = torch.zeros(0, dtype=torch.int32, device=dev)
             for k in on_host:                      # frames the host had to decode (files the index refused) lie in the arena as they are
                 at, to, n = int(A.file_off[idx[k]]), int(frames[k, 0]), int(A.size[idx[k]])
                 src[to:to + n].copy_(A.data[at:at + n], non_blocking=True)
             if self.pipeline.random:
-                epoch = int(getattr(self.sampler, 'epoch', 0))
-                words = key_words((self.seed, epoch, self.rank) + tuple(key_tail))
-                rec, gb, gl, gc, diag = device_parts([B * 80, B * G * 16, B * G * 4, B * 4, B * 8], dev)
-                N.call('t3d_detect_draw', self._cfg.ctypes.data, len(self._cfg), words.ctypes.data, len(words), N.ptr(part(0, torch.uint8, -1)),
-                       B, N.ptr(A.d_boxes), N.ptr(A.d_labels), N.ptr(A.d_box_start), len(A), len(A.labels), G, N.ptr(rec), N.ptr(gb),
-                       N.ptr(gl), N.ptr(gc), N.ptr(diag), N.stream())
+                if not crop:
+                    rec, gb, gl, gc = self._draw(part, B, key_tail, dev)
                 N.call('t3d_detect_augment_u8', N.ptr(src), src.numel(), N.ptr(rec), N.ptr(imgs), B, oh, ow, N.stream())
                 out = (imgs, gb.view(torch.float32).view(B, G, 4), gl.view(torch.int32).view(B, G), gc.view(torch.int32))
             else:
                 N.call('t3d_augment_crops_u8', N.ptr(src), src.numel(), N.ptr(part(3, torch.uint8, -1)), N.ptr(imgs), B, oh, ow, N.stream())
                 out = (imgs, part(4, torch.float32, B, G, 4), part(5, torch.int32, B, G), part(6, torch.int32, B), part(7, torch.int32, B, 2))
         return out, self._ready(stream, prefetch)
+
+    def _draw(self, part, B, key_tail, dev):
+        """Enqueue t3d_detect_draw for the uploaded frame table -> uint8 device views (records, gt_boxes, gt_labels, gt_counts)."""
+        from .. import _native as N
+        A, G = self.arena, self.arena.G
+        epoch = int(getattr(self.sampler, 'epoch', 0))
+        words = key_words((self.seed, epoch, self.rank) + tuple(key_tail))
+        rec, gb, gl, gc, diag = device_parts([B * 80, B * G * 16, B * G * 4, B * 4, B * 8], dev)
+        N.call('t3d_detect_draw', self._cfg.ctypes.data, len(self._cfg), words.ctypes.data, len(words), N.ptr(part(0, torch.uint8, -1)),
+               B, N.ptr(A.d_boxes), N.ptr(A.d_labels), N.ptr(A.d_box_start), len(A), len(A.labels), G, N.ptr(rec), N.ptr(gb),
+               N.ptr(gl), N.ptr(gc), N.ptr(diag), N.stream())
+        return rec, gb, gl, gc
 
     def __iter__(self):
         order, bs = self._order(), self.batch_size

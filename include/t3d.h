@@ -588,6 +588,48 @@ int t3d_jpeg_decode_roi_u8(const unsigned char* data, long long data_bytes, cons
                            long long out_bytes, void* work, long long work_bytes, long long total_blocks, int* status, int B,
                            long long max_lanes, int max_blocks, long long max_runs, void* stream);
 
+/* t3d_detect_roi_plan: the join of t3d_detect_draw and t3d_jpeg_decode_roi_u8 ON THE DEVICE, one launch, no read-back
+ * (csrc/detect_roi.hip, csrc/detect_roi.h; torchdet3d/dataloaders/detection_arena.py, crop_decode).  t3d_detect_draw reads no
+ * pixel, so it can run BEFORE the decode; this call turns its records into the rectangle decode's tables, so that only the part
+ * of each frame that its crop reads is decoded, and rewrites the records so that t3d_detect_augment_u8, unchanged, makes the same
+ * image from the part as from the whole frame, bit for bit.
+ * t3d_detect_roi_plan_host is the same arithmetic on the CPU: the same arguments, every pointer a HOST pointer, `stream`
+ * ignored; HOST ONLY, no HIP call, never initialises the GPU.  tests/test_detect_roi_plan_host.py holds it to numpy.
+ *   records [B] t3d_det_sample, IN AND OUT: the planned samples' records are rewritten in place, every other one is not touched
+ *   sample int32 [n]       item j belongs to record sample[j], each record at most once (NULL: item j to record j); an index
+ *                          outside [0, B) plans the whole frame
+ *   infos [n], items [n]   the frames' t3d_jpeg_info rows and the WHOLE-FRAME t3d_jpeg_item of t3d_jpeg_decode_u8 (file_offset:
+ *                          the file; seg_offset: its first segment; out_offset, block_offset: prefix sums of whole frames)
+ *   src_bytes              the size of the buffer the frames are decoded into (t3d_detect_augment_u8's src_bytes)
+ *   roi_items [n], rects int32 [n][12], diag int32 [n][2]: OUT
+ * The source rectangle is the crop intersected with the pasted frame, turned back to source pixels.  With (rw, rh) the turned frame -- (w, h) for
+ * turns 0, (h, w) for turns 1 and 3 -- a0 = max(cx0 - left, 0), a1 = min(cx1 - left, rw), b0 = max(cy0 - top, 0),
+ * b1 = min(cy1 - top, rh):
+ *     turns 0: x in [a0, a1), y in [b0, b1)     turns 1: x in [w - b1, w - b0), y in [a0, a1)
+ *     turns 3: x in [b0, b1), y in [h - a1, h - a0)
+ * exactly, no slack: the bilinear taps of t3d_detect_augment_u8 never leave [cx0, cx1 - 1] x [cy0, cy1 - 1].  An empty
+ * intersection (a crop wholly in the fill) gives (0, 0, 1, 1).
+ *   rects row     x0 y0 x1 y1, the MCU rectangle the decode's own rule gives for it (csrc/jpeg_decode.h: roi_mcus),
+ *                 seg_first = (my0 * mcus_x + mx0) / seg_mcus, seg_count up to segment ((my1 - 1) * mcus_x + mx1 - 1) / seg_mcus, 0 0
+ *   item          file_offset + scan_offset, scan_bytes, reserved 0 (the whole scan, which is resident); seg_offset + seg_first;
+ *                 out_offset and block_offset COPIED: the part lies packed at the start of its frame's slot and its blocks at the
+ *                 start of its frame's share of the workspace, so no sum over the batch is needed and the host's whole-frame
+ *                 totals and bounds remain upper bounds of the decode call
+ *   record        offset = out_offset; h, w = the rectangle's; (left, top) += (x0, y0) for turns 0, (y0, w - x1) for turns 1,
+ *                 (h - y1, x0) for turns 3, with the ORIGINAL h, w (saturated at 2^31 - 1): the part lies where it lay in the
+ *                 canvas; every other field stays
+ *   diag          the rectangle's pixels and the MCU rectangle's 8x8 blocks (saturated at 2^31 - 1)
+ * A record that t3d_detect_augment_u8 would refuse (judged with src_bytes), one whose h, w are not the info's, or a missing one
+ * is NOT rewritten and gets the whole frame: that sample behaves as without this call.  An info row whose h, w, sampling,
+ * MCU grid or seg_mcus the indexer would not write gets the whole-frame tables as they stand and diag (0, 0);
+ * t3d_jpeg_decode_roi_u8 refuses it (status 2).  Every range written here is checked again there and by t3d_detect_augment_u8 before anything is read.
+ * One sample a lane.  T3D_ERR_ARG, nothing launched: B or n < 0 or > 65535, src_bytes < 0, with n > 0 a NULL pointer (but
+ * sample).  n == 0 returns T3D_OK. */
+int t3d_detect_roi_plan(void* records, int B, const int* sample, const t3d_jpeg_info* infos, const t3d_jpeg_item* items, int n,
+                        long long src_bytes, t3d_jpeg_item* roi_items, int* rects, int* diag, void* stream);
+int t3d_detect_roi_plan_host(void* records, int B, const int* sample, const t3d_jpeg_info* infos, const t3d_jpeg_item* items, int n,
+                             long long src_bytes, t3d_jpeg_item* roi_items, int* rects, int* diag, void* stream);
+
 /* The MCU index BUILT ON THE DEVICE (csrc/jpeg_scan.h, csrc/jpeg_scan.hip): for a frame nobody has indexed -- a video or camera
  * frame -- the host reads only the markers (t3d_jpeg_header) and the device finds the MCU starts and DC predictors of every
  * frame of a batch (t3d_jpeg_index_device).  The rows are t3d_jpeg_index's, byte for byte; t3d_jpeg_decode_u8 runs behind it

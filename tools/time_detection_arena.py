@@ -11,10 +11,21 @@ are those of tools/time_jpeg_decode.py (generated 1440 x 1920, quality 90, 4:2:0
         16 workers on the same files, --alternations times; one line per epoch, then medians, ranges and the one condition:
         the arena's whole-epoch rate lies above the decode='device' loader's by more than that loader's min - max spread;
   d.    `DetectorTrainer.train` over the arena loader (frames / s of the epoch) beside the step time on one resident batch.
+  crop  (not in the default list) `ArenaDetectionLoader(crop_decode=True)` beside the same loader with the flag off, per
+        seg_mcus of --crop-seg-mcus: first the 5 + --reps timed keys give the same batches either way and the planner's diag
+        gives the mean share of frame pixels and of 8x8 blocks it asked for; then --rounds rounds of device-event time of one
+        arena batch, flag off and on alternating batch by batch (5 warm-up, --reps timed), median and min - max, and the
+        condition: the flag-on median lies below the flag-off minimum; the verdict -- that condition in every round at the
+        seg_mcus of the lowest flag-on median; then `DetectorTrainer.train` over --train-batches batches, off and on twice
+        alternating, beside the step time on one resident batch.  (The flag-off path is the code before the flag existed:
+        part b. with T3D_LIB set to a build of that library is the control.)
+  crop_trace  5 + --reps batches with --crop-decode 0 or 1 at the first seg_mcus of --crop-seg-mcus and nothing timed: the run
+        a kernel trace is taken of from outside (the whole-frame memset, entropy, IDCT, colour, planner, draw, augment).
 Every part runs under its own time limit (SIGALRM in this one process; --limit seconds a part) and the tool stops at the first
 failure or expired limit.
 Usage: python tools/time_detection_arena.py [--batch 80] [--reps 50] [--alternations 5] [--epoch-batches 200]
-       [--loader-batch 16] [--files 80] [--parts fill,a,b,c,d] [--limit 600] [--out FILE]"""
+       [--loader-batch 16] [--files 80] [--parts fill,a,b,c,d] [--limit 600] [--out FILE]
+       [--crop-seg-mcus 1,2,4] [--rounds 3] [--train-batches 40] [--crop-decode 1]"""
 import argparse
 import contextlib
 import json
@@ -75,6 +86,10 @@ def main():
     ap.add_argument('--files', type=int, default=80)
     ap.add_argument('--parts', default='fill,a,b,c,d')
     ap.add_argument('--limit', type=int, default=600)
+    ap.add_argument('--crop-seg-mcus', default='1,2,4')
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--train-batches', type=int, default=40)
+    ap.add_argument('--crop-decode', type=int, default=1, choices=(0, 1))
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'this measurement needs the GPU'
@@ -214,6 +229,90 @@ def main():
                 emit(what='DetectorTrainer.train over the arena loader', B=B, batches=n, ms_per_step_in_the_epoch=round(dt / n * 1e3, 3),
                      frames_per_s=round(n * B / dt, 1), ms_per_step_on_one_resident_batch=round(step_ms, 3),
                      frames_per_s_on_one_resident_batch=round(B / step_ms * 1e3, 1))
+        if 'crop' in parts or 'crop_trace' in parts:
+            segs = [int(s) for s in a.crop_seg_mcus.split(',')]
+
+            def pair(seg):
+                d = ObjectronFrames(root, 'train', decode='device')
+                d.build_index(os.path.join(root, f'index_seg{seg}.npy'), threads=16, seg_mcus=seg)
+                ar = DetectionArena(d).fill()
+                return ar, [ArenaDetectionLoader(ar, pipe, B, seed=3, prefetch=0, crop_decode=flag) for flag in (False, True)]
+
+            def one(ld, r):
+                idx = order[(r * B) % (len(ds) - B):][:B]
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = ld.finish(idx, (r,), prefetch=0)
+                e1.record()
+                e1.synchronize()
+                assert not ld.last_status.any().item()
+                return out, e0.elapsed_time(e1), idx
+        if 'crop_trace' in parts:                   # (for a kernel trace from outside: 55 batches of one flag, nothing timed)
+            with limit(a.limit, 'crop_trace'):
+                _, lds = pair(segs[0])
+                for r in range(5 + a.reps):
+                    one(lds[a.crop_decode], r)
+                emit(what='arena batches for a kernel trace', B=B, batches=5 + a.reps, seg_mcus=segs[0], crop_decode=bool(a.crop_decode))
+        if 'crop' in parts:
+            best, rounds_won = None, {}
+            with limit(4 * a.limit, 'crop'):
+                for seg in segs:
+                    ar, (off, on) = pair(seg)
+                    # the timed keys give the same batches either way; what the planner asked for, from its diag
+                    px, bl = [], []
+                    for r in range(5 + a.reps):
+                        (want, _, idx), (got, _, _) = one(off, r), one(on, r)
+                        assert all(torch.equal(u, v) for u, v in zip(got, want)), f'seg_mcus {seg}, batch {r}: the batches differ'
+                        d = on.last_crop_diag.cpu().numpy().astype(np.float64)
+                        px.append(float(np.mean(d[:, 0] / (ar.h[idx] * ar.w[idx]))))
+                        bl.append(float(np.mean(d[:, 1] / ar.blocks[idx])))
+                    emit(what='crop decode: the planner asked for', seg_mcus=seg, B=B, batches=5 + a.reps, batches_equal=True,
+                         mean_share_of_frame_pixels=round(float(np.mean(px)), 4), mean_share_of_frame_blocks=round(float(np.mean(bl)), 4))
+                    wins = []
+                    for k in range(a.rounds):
+                        ms = ([], [])
+                        for r in range(5 + a.reps):              # flag off and on alternating, batch by batch, on the same key
+                            for flag in (0, 1):
+                                t = one((off, on)[flag], r)[1]
+                                if r >= 5:
+                                    ms[flag].append(t)
+                        wins.append(bool(np.median(ms[1]) < min(ms[0])))
+                        emit(what='one arena batch on the device, crop decode off / on', seg_mcus=seg, B=B, round=k, off=stats(ms[0], 1.0, 'ms'),
+                             on=stats(ms[1], 1.0, 'ms'), on_median_below_off_min=wins[-1])
+                        if best is None or np.median(ms[1]) < best[1]:
+                            best = (seg, float(np.median(ms[1])))
+                    rounds_won[seg] = wins
+                    del ar, off, on
+                    torch.cuda.empty_cache()
+                emit(what='crop decode: verdict', best_seg_mcus=best[0], rule='on median below off min in every round, at the best seg_mcus',
+                     gain=all(rounds_won[best[0]]), rounds=rounds_won[best[0]])
+            with limit(a.limit, 'crop: train'):
+                from torchdet3d.models.ssd import SSD300
+                from torchdet3d.trainer import DetectorTrainer
+                ar, _ = pair(best[0])
+                walk = np.tile(order, -(-a.train_batches * B // len(order)))[:a.train_batches * B]
+                line = {}
+                for flag in (False, True, False, True):
+                    tr = DetectorTrainer(SSD300(device='cuda:0', dtype=torch.bfloat16, seed=0), print_freq=1 << 30)
+                    ld = ArenaDetectionLoader(ar, pipe, B, indices=walk, drop_last=True, seed=1, crop_decode=flag)
+                    if 'resident' not in line:
+                        batch = next(iter(ld))
+                        for _ in range(5):
+                            tr.train_step(*batch[:4])
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(20):
+                            tr.train_step(*batch[:4])
+                        torch.cuda.synchronize()
+                        line['resident'] = round((time.perf_counter() - t0) / 20 * 1e3, 3)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    tr.train(ld, 0)
+                    torch.cuda.synchronize()
+                    line.setdefault('on' if flag else 'off', []).append(round((time.perf_counter() - t0) / len(ld) * 1e3, 3))
+                    del tr, ld
+                emit(what='DetectorTrainer.train over the arena loader, crop decode off / on', B=B, batches=a.train_batches, seg_mcus=best[0],
+                     ms_per_step_off=line['off'], ms_per_step_on=line['on'], ms_per_step_on_one_resident_batch=line['resident'])
 
 
 if __name__ == '__main__':
